@@ -22,7 +22,14 @@ when fewer than N GPUs are visible or WORLD_SIZE != N.
 Synthetic data: games start from the empty board; weights are the counter-based random init of
 the named architecture (az_net_init_random on rank 0, broadcast to the other ranks).
 
-cpu_baseline (rank 0, N=1): the CPU restatement of the reference search (oracle/, Mode S) with the
+A plain run (`bench.py --gpus 1 --steps N --warmup W`) sets up, warms up, times the N moves and
+prints the result line; the trunk / tree kernel figures in it come from device clock stamps taken
+inside those moves.  `--dump-outputs DIR` also writes the records of the last timed move (what
+step() hands its caller) as DIR/<name>.npy.  `--full` adds the measurements that take time of
+their own: the CPU baseline before the GPU work and parity_mode (the fp32-faithful f16x3 trunk
+on the same live games) after the timed moves.
+
+cpu_baseline (--full, rank 0, N=1): the CPU restatement of the reference search (oracle/, Mode S) with the
 fp32 PyTorch-CPU network, one game per worker process, one thread each, on the host's CPU share
 (self_play_manager.cpp:69-89), timed over a fixed window.
 """
@@ -96,7 +103,15 @@ def parse(argv=None):
                     help="trunk precision: fp16 = the reference useFp16 option (fp16 MFMA operands, fp32 accumulate, "
                          "2^-20 residual stream), f16x3 = fp32-faithful (fp16 hi + lo pieces, three MFMAs per "
                          "product), bf16x3 = bf16 hi + lo pieces (the full fp32 range, ~2^-17)")
-    ap.add_argument("--cpu-baseline", type=int, default=1, help="time the CPU restatement on rank 0 at N=1")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure what the headline figure does not need: the CPU baseline (--cpu-baseline, "
+                         "before the GPU work) and parity_mode (--parity-steps, after the timed moves).  Off by "
+                         "default: a plain run sets up, warms up, times --steps moves and prints the line")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="after the timed moves, write what the last timed move returned to its caller (the MoveData "
+                         "records of every game: action, value, child count, action-indexed policy) as DIR/<name>.npy, "
+                         "float32 / float64; the inputs (seeds, weights, games) are the same from run to run")
+    ap.add_argument("--cpu-baseline", type=int, default=1, help="--full: time the CPU restatement on rank 0 at N=1")
     ap.add_argument("--cpu-window", type=float, default=20.0, help="seconds of the CPU baseline's timed window")
     ap.add_argument("--cpu-workers", type=int, default=0, help="CPU baseline processes (0: the host's CPU share, <=16)")
     ap.add_argument("--cpu-beside", type=int, default=0,
@@ -108,8 +123,8 @@ def parse(argv=None):
                          "(az_conv_flags | bits -> az_diag_set_conv_flags) for same-box A/B runs; the trunk "
                          "kernel the run dispatched is named in roofline.kernel")
     ap.add_argument("--parity-steps", type=int, default=2,
-                    help="N=1: after the timed moves, switch the live net to the fp32-faithful f16x3 trunk (the parity "
-                         "precision) and time this many more moves of the same games, reported as parity_mode; "
+                    help="--full, N=1: after the timed moves, switch the live net to the fp32-faithful f16x3 trunk (the "
+                         "parity precision) and time this many more moves of the same games, reported as parity_mode; "
                          "0 disables")
     ap.add_argument("--parity-warmup", type=int, default=0,
                     help="untimed parity-precision moves before parity_mode's timed ones (the piece sets are "
@@ -212,6 +227,21 @@ class GpuWorkload:
     def sync(self):
         pass                           # selfplayStep returns after a stream synchronize
 
+    def outputs(self):
+        """The MoveData records the last step() returned (--dump-outputs), as float arrays indexed by
+        game slot: action, value, n_children [games] and the visit policy scattered from child order
+        to actions [games, A].  A game that did not move in that step keeps action -1 / zeros.
+        thinking_time_ms is a wall-clock reading, not a result: left out."""
+        G, A = self.mcts_args["n_games"], self.desc.action_size
+        out = {"action": np.full(G, -1.0, np.float64), "value": np.zeros(G, np.float32),
+               "n_children": np.zeros(G, np.float64), "policy": np.zeros((G, A), np.float32)}
+        for slot, md in self.mcts.stepMoves(materialize=True):
+            out["action"][slot] = md.action
+            out["value"][slot] = md.value
+            out["n_children"][slot] = len(md.policy)
+            out["policy"][slot, md.child_actions] = md.policy
+        return out
+
     def close(self):
         """Free the device search, the net and the engine."""
         if self.mcts is not None:
@@ -310,6 +340,10 @@ class StreamWorkload:
     def sync(self):
         pass
 
+    def outputs(self):
+        subs = [w.outputs() for w in self.subs]           # the handles' games in global game order
+        return {k: np.concatenate([s[k] for s in subs]) for k in subs[0]}
+
     def close(self):
         self.pool.shutdown()
         for w in self.subs:
@@ -345,6 +379,29 @@ def _timed_moves(a, wl, net, steps, barrier):
             "tree_evictions": ev() if ev else None,
             "launches": launches, "forwards": forwards, "tree": wl.mcts.profile_read(),
             "kernel": net.trunk_kernel()}     # the kernel the library dispatches for this net (engine's own choice)
+
+
+DUMP_LIMIT = 64 * 10 ** 6      # bytes --dump-outputs writes at most
+
+
+def dump_outputs(path, arrays, rank=0, world=1):
+    """--dump-outputs: the workload's last-step arrays as <path>/<name>.npy (<name>.rank<r>.npy at
+    N>1), float32 / float64.  Past DUMP_LIMIT bytes in all, the same fixed, seeded sample of the
+    game rows of every array is written instead (and rows.npy names the rows)."""
+    arrays = {k: np.ascontiguousarray(v) for k, v in arrays.items()}
+    bad = [k for k, v in arrays.items() if v.dtype not in (np.float32, np.float64)]
+    if bad:
+        raise TypeError(f"--dump-outputs: {bad} not float32 / float64")
+    total = sum(v.nbytes for v in arrays.values())
+    if total > DUMP_LIMIT:
+        n = min(len(v) for v in arrays.values())
+        per_row = sum(v.nbytes // len(v) for v in arrays.values()) + 8
+        rows = np.sort(np.random.default_rng(0).choice(n, max(1, DUMP_LIMIT // per_row), replace=False))
+        arrays = {k: np.ascontiguousarray(v[rows]) for k, v in arrays.items()}
+        arrays["rows"] = rows.astype(np.float64)
+    os.makedirs(path, exist_ok=True)
+    for k, v in arrays.items():
+        np.save(os.path.join(path, k + (f".rank{rank}" if world > 1 else "") + ".npy"), v)
 
 
 def _roofline(a, m, precision):
@@ -486,6 +543,8 @@ def _run_rank(a, rank, world, sh, wl, net, coll, parity, before_timed=None):
         if coll is not None:
             coll.barrier()
     m = _timed_moves(a, wl, net, a.steps, barrier)
+    if getattr(a, "dump_outputs", None):
+        dump_outputs(a.dump_outputs, wl.outputs(), rank, world)      # the last timed move's records
     pm = None
     if parity is not None and world == 1:
         n_par = parity(1e3 * m["elapsed"] / a.steps)
@@ -771,7 +830,7 @@ def main(argv=None, make_workload=None, backend=None):
     # 259 pinned to CPUs of their own, against 349 alone (profiles/r06_bench_c3_cpu_pinned.json)
     cpu = {}
     cpu_thread = None
-    if a.cpu_baseline and world == 1:
+    if a.full and a.cpu_baseline and world == 1:
         import threading
         workers = a.cpu_workers or cpu_share()
         mine = sorted(os.sched_getaffinity(0)) if hasattr(os, "sched_getaffinity") else []
@@ -841,7 +900,8 @@ def main(argv=None, make_workload=None, backend=None):
             make_coll = lambda wl: TorchColl(dist, "cpu")                                 # noqa: E731
     try:
         parity = None
-        if world == 1 and a.parity_steps > 0 and a.precision not in ("f16x3", "bf16x3") and a.channels % 64 == 0:
+        if a.full and world == 1 and a.parity_steps > 0 and a.precision not in ("f16x3", "bf16x3") \
+                and a.channels % 64 == 0:
             parity = parity_budget(a)
         out = run_rank(a, rank, world, make_workload, make_coll, parity=parity, before_timed=join_cpu)
         join_cpu()

@@ -274,6 +274,83 @@ def test_bench_parity_mode_in_place_world1():
     assert wls[0].steps == 5 and wls[0].net.precision is None
 
 
+class _DumpWorkload(_Workload):
+    """A stand-in whose records name the step that made them."""
+
+    def outputs(self):
+        g = self.shard["games"]
+        return {"action": np.arange(g, dtype=np.float64) + self.steps,
+                "policy": np.full((g, 5), 0.25 * self.steps, np.float32)}
+
+
+def _main_line(bench, capsys, argv, cls=_Workload):
+    wls = []
+
+    def make(a_, local, shard):
+        wls.append(cls(a_, local, shard))
+        return wls[-1]
+    assert bench.main(argv, make_workload=make) == 0
+    import json
+    return json.loads(capsys.readouterr().out.strip().splitlines()[-1]), wls[0]
+
+
+def test_bench_plain_run_is_lean_and_full_adds_the_rest(monkeypatch, capsys):
+    """A plain run times its --steps moves and nothing else: no CPU baseline, no parity moves.
+    --full runs both, as the bench did by default before the option existed."""
+    import bench
+    for k in ("WORLD_SIZE", "RANK", "LOCAL_RANK"):
+        monkeypatch.delenv(k, raising=False)
+    calls = []
+
+    def fake_cpu(a, workers, window, cpus=None):
+        calls.append((workers, window))
+        return {"evals": 100, "evals_per_s": 50.0, "cores": workers, "window_s": 2.0}
+    monkeypatch.setattr(bench, "cpu_baseline", fake_cpu)
+    out, w = _main_line(bench, capsys, ["--gpus", "1", "--steps", "3", "--warmup", "2"])
+    assert w.steps == 2 + 3 and not calls and w.net.precision is None
+    assert "parity_mode" not in out and out["cpu_baseline"] is None
+    assert out["steps"] == 3 and out["warmup"] == 2 and out["dtype"] == "fp16" and out["unit"] == "positions/s"
+    assert out["metric"] == bench.METRIC and out["higher_is_better"] is True
+    assert out["value"] == pytest.approx(3 * 2048 / (3 * out["ms_per_step"] / 1e3))
+    assert out["roofline"]["frac"] > 0 and "k_select" in out["tree_kernels"]      # in-run figures stay
+    out, w = _main_line(bench, capsys, ["--gpus", "1", "--steps", "3", "--warmup", "2", "--full", "--cpu-workers", "2"])
+    assert w.steps == 2 + 3 + 2 and calls == [(2, 20.0)] and w.net.precision == bench.PREC["f16x3"]
+    assert out["parity_mode"]["dtype"] == "f16x3" and out["parity_mode"]["steps"] == 2
+    assert out["cpu_baseline"]["value"] == pytest.approx(50.0 / 800) and out["cpu_baseline"]["cores"] == 2
+    assert out["steps"] == 3 and out["value"] == pytest.approx(3 * 2048 / (3 * out["ms_per_step"] / 1e3))
+
+
+def test_bench_dump_outputs(monkeypatch, capsys, tmp_path):
+    """--dump-outputs DIR writes the records of the LAST TIMED move (before any parity move) as
+    DIR/<name>.npy in float32 / float64; past the byte limit, the same seeded sample of game rows
+    of every array; a workload with nothing to hand over, or a non-float array, is an error."""
+    import bench
+    for k in ("WORLD_SIZE", "RANK", "LOCAL_RANK"):
+        monkeypatch.delenv(k, raising=False)
+    d = tmp_path / "dump"
+    argv = ["--gpus", "1", "--steps", "3", "--warmup", "2", "--full", "--cpu-baseline", "0", "--dump-outputs", str(d)]
+    _, w = _main_line(bench, capsys, argv, _DumpWorkload)
+    assert w.steps == 7 and sorted(p.name for p in d.iterdir()) == ["action.npy", "policy.npy"]
+    act, pol = np.load(d / "action.npy"), np.load(d / "policy.npy")
+    assert act.dtype == np.float64 and pol.dtype == np.float32 and pol.shape == (2048, 5)
+    assert np.array_equal(act, np.arange(2048.0) + 5) and np.all(pol == 0.25 * 5)
+    with pytest.raises(AttributeError):
+        _main_line(bench, capsys, argv, _Workload)
+    with pytest.raises(TypeError):
+        bench.dump_outputs(str(tmp_path / "bad"), {"slot": np.arange(4)})
+    # the byte limit: a fixed sample of rows, the same rows of every array and from call to call
+    monkeypatch.setattr(bench, "DUMP_LIMIT", 4096)
+    arrs = w.outputs()
+    bench.dump_outputs(str(tmp_path / "a"), arrs)
+    bench.dump_outputs(str(tmp_path / "b"), arrs)
+    got = {p.name: np.load(p) for p in (tmp_path / "a").iterdir()}
+    assert sorted(got) == ["action.npy", "policy.npy", "rows.npy"] and sum(v.nbytes for v in got.values()) <= 4096
+    rows = got["rows.npy"].astype(int)
+    assert 1 < len(rows) < 2048 and np.all(np.diff(rows) > 0)
+    assert np.array_equal(got["action.npy"], arrs["action"][rows]) and np.array_equal(got["policy.npy"], arrs["policy"][rows])
+    assert all(np.array_equal(v, np.load(tmp_path / "b" / k)) for k, v in got.items())
+
+
 class _FakeDist:
     """Stands in for az_amd.dist.Dist (the engine's RCCL communicator) on CPU: records the id it
     was given; its collectives run over the gloo group so the bench's reductions stay real."""

@@ -10,4 +10,4 @@ O=$R/gpurun_out/${TAG:-adhoc}
 mkdir -p $O
 TAG=${TAG:-adhoc}/t LIMIT=600 FILES="${FILES:-tests/test_gpu_search.py tests/test_gpu_callback_eval.py}" bash tools/gpu_tests.sh &&
 { [ -z "$AB" ] || ABTAG=${TAG:-adhoc}/ab ROUNDS=${ROUNDS:-3} bash tools/ab_builds.sh; } &&
-{ [ "${BENCH:-1}" = 0 ] || { timeout -k 10 590 python3 bench.py --steps ${STEPS:-20} --warmup ${WARMUP:-5} > $O/bench_c3.json 2> $O/bench_c3.err && tail -c 600 $O/bench_c3.json; }; }
+{ [ "${BENCH:-1}" = 0 ] || { timeout -k 10 590 python3 bench.py --full --steps ${STEPS:-20} --warmup ${WARMUP:-5} > $O/bench_c3.json 2> $O/bench_c3.err && tail -c 600 $O/bench_c3.json; }; }
