@@ -10,6 +10,7 @@ import os
 import numpy as np
 import pytest
 
+from replay_util import compare_roots, replay_eval_log
 from test_gpu_search import bits, children_rows, play_and_compare
 
 GOLD = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden")
@@ -112,22 +113,8 @@ def test_gpu_go_net_selfplay_matches_oracle_replay(engine, prec):
         m.close()
     assert len(pol) > sims and planes.shape[1] == 8
 
-    k = [0]
-
-    def replay(game, x):
-        i = k[0]
-        k[0] += 1
-        assert np.array_equal(x, planes[i]), f"feature planes differ at evaluation {i}"
-        return pol[i], float(valv[i])
-
-    ref = O.play(bs=bs, sims=sims, max_moves=len(dev), eval_kind=O.EVAL_REPLAY, evaluator=replay,
-                 noise_seed=42 + logged, game=O.GAME_GO)[0]
-    assert k[0] == len(pol)
-    for ply, (d, r) in enumerate(zip(dev, ref["moves"])):
-        kids = r["children"]
-        assert d["N"] == [c[1] for c in kids] and d["VL"] == [c[2] for c in kids], ply
-        assert d["W"] == [c[3] for c in kids] and d["P"] == [c[4] for c in kids], ply
-        assert d["probs"] == r["probs"] and d["action"] == r["action"], ply
+    ref = replay_eval_log(pol, valv, planes, [(logged, len(dev))], bs=bs, sims=sims, game=O.GAME_GO)[0]
+    compare_roots(dev, ref["moves"], value=False)
     # the logged network outputs against the fp32 reference network on the same planes
     rl, rv = net_oracle.forward(desc, blob, planes[:64])
     sm = net_oracle.softmax_policy(rl)
@@ -183,22 +170,8 @@ def test_gpu_c4_full_size_replay(engine, G, logged, prec, kernel):
         pol, valv, planes = m.readEvalLog(cap)
     finally:
         m.close()
-    k = [0]
-
-    def replay(game, x):
-        i = k[0]
-        k[0] += 1
-        assert np.array_equal(x, planes[i]), f"feature planes differ at evaluation {i}"
-        return pol[i], float(valv[i])
-
-    ref = O.play(bs=bs, sims=sims, max_moves=moves, eval_kind=O.EVAL_REPLAY, evaluator=replay,
-                 noise_seed=42 + logged, game=O.GAME_GO)[0]
-    assert k[0] == len(pol)
-    for ply, (d, r) in enumerate(zip(dev, ref["moves"])):
-        kids = r["children"]
-        assert d["N"] == [c[1] for c in kids] and d["VL"] == [c[2] for c in kids], ply
-        assert d["W"] == [c[3] for c in kids] and d["P"] == [c[4] for c in kids], ply
-        assert d["probs"] == r["probs"] and d["action"] == r["action"], ply
+    ref = replay_eval_log(pol, valv, planes, [(logged, moves)], bs=bs, sims=sims, game=O.GAME_GO)[0]
+    compare_roots(dev, ref["moves"], value=False)
     idx = np.random.default_rng(1).choice(len(pol), 32, replace=False)
     rl, rv = net_oracle.forward(desc, blob, planes[idx])
     assert np.abs(net_oracle.softmax_policy(rl) - pol[idx]).max() <= 1e-4 and np.abs(rv - valv[idx]).max() <= 1e-4

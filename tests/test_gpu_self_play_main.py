@@ -70,3 +70,55 @@ def test_gpu_self_play_binary_dist_path(tmp_path):
     assert md["job_total_moves"] == md["total_moves"] == 8 * 4 and md["job_games_completed"] == 8
     assert len(glob.glob(str(out / "0*_*.json"))) == 8
     assert "Job: 8 games, 32 moves" in r.stdout
+
+
+@pytest.mark.gpu
+def test_gpu_self_play_binary_with_net_matches_in_process(tmp_path):
+    """The binary with a device network, played to completion: 7 games of 6x6 Gomoku on 3 slots
+    (--batch-size 3) with a random-init 2 x 32 net in f32.  Its record files equal, game by game, the
+    records of the same run made in-process -- HipNeuralNetwork.init_random(7) (net_oracle.init_blob,
+    test_gpu_net_init_random_matches_numpy), SelfPlayManager with the binary's search settings (fpu
+    0.1, root noise on every search, noise seed 42 + game id: shardGames(0, 1, 7, 42) and
+    SelfPlayManager::setShard) -- the configuration whose oracle replay
+    test_gpu_net_selfplay_run_matches_oracle_replay[binary-cfg] verifies."""
+    import az_amd
+    n, slots, bs, sims, seed = 7, 3, 6, 32, 7
+    out = tmp_path / "games"
+    r = subprocess.run([BIN, "--game", "gomoku", "--size", str(bs), "--num-games", str(n), "--batch-size", str(slots),
+                        "--simulations", str(sims), "--net-blocks", "2", "--net-channels", "32", "--seed", str(seed),
+                        "--precision", "f32", "--output-dir", str(out), "--threads", "4"],
+                       capture_output=True, text=True, timeout=240)
+    assert r.returncode == 0, r.stdout + r.stderr
+    eng = az_amd.Engine(0)
+    desc = az_amd.gomoku_net_desc(board_size=bs, channels=32, blocks=2, precision=az_amd.AZ_PREC_F32, max_batch=slots)
+    net = az_amd.HipNeuralNetwork(eng, desc)
+    net.init_random(seed)
+    mgr = az_amd.SelfPlayManager(eng, net=net, numGames=slots, numSimulations=sims, board_size=bs, fpu_reduction=0.1,
+                                 use_dirichlet_each_search=True, noise_seed=42, noise_seed_stride=1)
+    try:
+        twins = mgr.generateGames(totalGames=n)
+    finally:
+        mgr.mcts.close()
+        net.close()
+    assert [t.game_id for t in twins] == list(range(n))
+    for g, twin in enumerate(twins):
+        files = glob.glob(str(out / f"{g:03d}_*.json"))
+        assert len(files) == 1, g
+        rec = json.load(open(files[0]))
+        assert rec["board_size"] == bs and len(rec["moves"]) == len(twin.moves) > 0, g
+        for ply, (mv, tm) in enumerate(zip(rec["moves"], twin.moves)):
+            assert mv["action"] == tm.action, (g, ply)
+            # JSON keeps no NaN payload (null): the T = 0 NaN entries are compared as NaNs
+            tp = np.asarray(tm.policy, np.float32)
+            assert len(mv["policy"]) == len(tp) and all((p is None) == bool(np.isnan(t)) for p, t in zip(mv["policy"], tp)), \
+                (g, ply)
+            assert _bits([0.0 if p is None else p for p in mv["policy"]]) == \
+                _bits(np.where(np.isnan(tp), np.float32(0.0), tp)), (g, ply)
+            assert _bits([mv["value"]])[0] == _bits([tm.value])[0], (g, ply)
+        assert rec["result"] == twin.result, g
+    md = [json.load(open(f)) for f in glob.glob(str(out / "metadata_*.json"))]
+    assert len(md) == 1
+    md = md[0]
+    assert (md["num_games_requested"], md["num_games_completed"]) == (n, n)
+    assert md["total_moves"] == sum(len(t.moves) for t in twins)
+    assert md["precision"] == "f32" and md["fp16_used"] is False and md["world"] == 1
