@@ -1832,11 +1832,6 @@ static void v6_launch(const ConvBf16Args& a, int mode, hipStream_t st) {
     else v6_launch_g<HB, false>(a, mode, st);
 }
 
-bool az_conv_v7_supported(const ConvBf16Args& a);
-int az_conv_v7_launch(const ConvBf16Args& a, int mode, int geo15, hipStream_t st);
-int az_conv_v7_tm(const ConvBf16Args& a);
-int az_conv_v7_ring(const ConvBf16Args& a);
-
 // Which kernel az_conv_g8_launch takes for a layer (a.flags already set): 0 none (unsupported),
 // 1 conv3x3_v7 (*geo = its 15x15 tile geometry), 2 conv3x3_v6 (*geo = 1 when DENSE), 3 conv3x3_v5.
 static int g8_choice(const ConvBf16Args& a, int* geo) {

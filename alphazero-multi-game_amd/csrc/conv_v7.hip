@@ -1260,8 +1260,6 @@ static void v7_launch_g(const ConvBf16Args& a, int mode, hipStream_t st) {
 }
 // DENSE boards: the tile rows (256 / 128 / 64) for this launch -- small batches take smaller tiles
 // so one round of blocks covers the CUs (az_conv_v7_tm; flag bits 0x70000 force 256 / 128 / 64 / 192)
-int az_conv_v7_tm(const ConvBf16Args& a);
-int az_conv_v7_ring(const ConvBf16Args& a);
 template <int HB>
 static void v7_launch_dense(const ConvBf16Args& a, int mode, hipStream_t st) {
     const bool r3 = az_conv_v7_ring(a) == 3;
@@ -1340,7 +1338,6 @@ static void v7x3_launch_g(const ConvBf16Args& a, hipStream_t st) {
     else hipLaunchKernelGGL((conv3x3_v7x3<HB, GEO, 1>), dim3(grid), dim3(256), 0, st, a);
 }
 
-int az_conv_flags();
 // first-round stagger (ns; az_diag_set_v9_stagger): 32 us measured best of 0 / 8 / 16 / 32 / 64 us,
 // -0.8 % per C3 launch, -0.7 % C4 (profiles/r04_v9x3_stagger.txt); only on launches of >= 1024 blocks
 // (several rounds), where a one-off delay of the last-started CU is amortised

@@ -16,12 +16,7 @@
 #include <vector>
 
 #include "engine_internal.h"
-#include "tree.h"
-
-__global__ void k_dataset_extract(DatasetDev d, TreeDev t);
-__global__ void k_dataset_gather(const float* states, const float* policy, const int* plen, const float* value, int row,
-                                 int NA, const long long* idx, int n, float* ostates, float* opolicy, int* oplen,
-                                 float* ovalue);
+#include "tree_kernels.h"
 
 struct az_dataset {
     az_engine* e = nullptr;

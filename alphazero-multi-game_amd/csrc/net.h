@@ -1,4 +1,6 @@
-// net.h -- launch interface of the ConvNet kernels (net_kernels.hip, conv_bf16.hip).
+// net.h -- launch interface of the ConvNet kernels (net_kernels.hip, conv_bf16.hip, conv_v7.hip,
+// smallnet.hip): the one declaration of every launcher, included by the file that defines it and
+// by every file that calls it.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -66,7 +68,7 @@ struct SmallNetArgs {
     int rec_identity;               // with rec: gidx[b] == b (the search's identity batch): gidx not read
     const int* m_limit;             // device: active boards
     const uint16_t* W;              // [2*blocks+1][9][64 n][64 c] fp16, BN folded; layer 0 = input conv (c >= planes zero)
-    const uint16_t* Wf;             // the same, fragment-major [layer][tap][kk][J][64 lanes][8] (engine.hip)
+    const uint16_t* Wf;             // the same, fragment-major [layer][tap][kk][J][64 lanes][8] (weight_pack.h)
     const float* bias;              // [2*blocks+1][64]
     const float* Wpc; const float* bpc;   // policy 1x1 conv [HC][64], [HC] (BN folded)
     const float* Wvc; const float* bvc;   // value 1x1 conv
@@ -119,3 +121,39 @@ void az_launch_se_residual(const float* y, const float* x, float* out, const flo
 // 1x1 GEMM with fp16 operands (rounded from fp32 on load), fp32 accumulation, bias + ReLU
 // (gemm_h16_relu: the fp16 rand-wire routers; taps == 1, K % 4 == 0, Am slices or A)
 void az_launch_gemm_h16_relu(const GemmArgs& p, hipStream_t st);
+void az_launch_rec_planes(const uint8_t* rec, float* dst, const int* eval_games, const int* n_eval, int go, int bs, int maxB,
+                          hipStream_t st);
+
+// ---- conv_bf16.hip: the 3x3 trunk convs on 16-bit operands, layout conversions, g8 pool
+int az_conv_flags();                  // kernel variant bits (az_diag_set_conv_flags)
+void az_conv_bf16_launch_v(const ConvBf16Args& a, bool split, hipStream_t st);
+int az_conv_bf16_name(const ConvBf16Args& a, int mode, char* out, int len);
+bool az_conv_v4_supported(int H, int W, int C, int N);
+void az_conv_v4_launch(const ConvBf16Args& a, int mode, hipStream_t st);
+bool az_conv_g8_supported(int H, int W, int C, int N);
+int az_conv_g8_launch(const ConvBf16Args& a, int mode, hipStream_t st);
+int az_conv_g8_name(const ConvBf16Args& a, int mode, char* out, int len);
+void az_launch_to_g8(const float* in, uint16_t* hi, int8_t* q, int C, int HW, const int* m_limit, int maxB, int mode,
+                     hipStream_t st, int Cout = 0);
+void az_launch_rec_to_g8(const uint8_t* rec, const int* gidx, uint16_t* hi, int go, int bs, const int* m_limit, int maxB,
+                         int mode, hipStream_t st, int NG = 2);
+void az_launch_to_g8x3(const float* in, uint16_t* hi, uint16_t* lo, int C, int HW, const int* m_limit, int maxB,
+                       hipStream_t st, int pt, int* ovf);
+void az_launch_to_f16(const float* in, uint16_t* out, size_t n, const int* m_limit, int rows_per_sample, int C,
+                      hipStream_t st, int* ovf);
+void az_launch_split_bf16(const float* in, uint16_t* hi, uint16_t* lo, size_t n, const int* m_limit, int rows_per_sample,
+                          int C, hipStream_t st);
+void az_launch_pool_g8(const uint16_t* hi, const int8_t* q, float* out, int B, int C, int H, int P, const int* m_limit,
+                       int mode, hipStream_t st);
+bool az_pool_heads_supported(int C, int H, int P, int N);
+int az_launch_pool_heads_g8(const uint16_t* hi, const int8_t* q, const float* Wt, const float* bias, float* out, int B,
+                            int C, int H, int P, int N, const int* m_limit, int mode, hipStream_t st);
+
+// ---- conv_v7.hip: conv3x3_v7 (taken by az_conv_g8_launch) and the x3 trunk convs (v7x3 / v9x3)
+bool az_conv_v7_supported(const ConvBf16Args& a);
+int az_conv_v7_launch(const ConvBf16Args& a, int mode, int geo15, hipStream_t st);
+int az_conv_v7_tm(const ConvBf16Args& a);     // DENSE boards: the tile rows (256 / 128 / 64) for this launch
+int az_conv_v7_ring(const ConvBf16Args& a);
+bool az_conv_v7x3_supported(const ConvBf16Args& a);
+int az_conv_v7x3_launch(const ConvBf16Args& a, hipStream_t st);
+int az_conv_x3_name(const ConvBf16Args& a, char* out, int len);

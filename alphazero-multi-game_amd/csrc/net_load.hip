@@ -1,0 +1,379 @@
+// net_load.hip -- parameter blob -> device weights of an az_net: the blob layouts, the packing of
+// every layer into the kernels' formats (arithmetic in weight_pack.h; allocation and upload here),
+// random initialisation and the weight entry points of include/az_engine.h.
+#include <hip/hip_runtime.h>
+
+#include <algorithm>
+#include <cmath>
+#include <cstring>
+#include <mutex>
+#include <vector>
+
+#include "../../include/az_engine.h"
+#include "engine_internal.h"
+#include "net.h"
+#include "net_host.h"
+#include "weight_pack.h"
+
+namespace {
+
+using namespace wpack;
+
+uint64_t splitmix64(uint64_t x) {
+    x += 0x9E3779B97F4A7C15ULL;
+    x = (x ^ (x >> 30)) * 0xBF58476D1CE4E5B9ULL;
+    x = (x ^ (x >> 27)) * 0x94D049BB133111EBULL;
+    return x ^ (x >> 31);
+}
+
+size_t count_params(const az_net_desc& d) {
+    const size_t F = d.channels, Ci = d.in_planes, HC = d.head_channels, PP = (size_t)d.pool * d.pool;
+    size_t n = 0;
+    auto conv = [&](size_t co, size_t ci, size_t k) { n += co * ci * k * k + (d.conv_bias ? co : 0) + 4 * co; };
+    conv(F, Ci, 3);
+    for (int i = 0; i < d.blocks; ++i) { conv(F, F, 3); conv(F, F, 3); }
+    conv(HC, F, 1);
+    n += (size_t)d.action_size * HC * PP + d.action_size;
+    conv(HC, F, 1);
+    n += (size_t)d.fc_hidden * HC * PP + d.fc_hidden;
+    n += (size_t)d.fc_hidden + 1;
+    return n;
+}
+
+// Blob layout of a rand-wire net: (count, init kind, fan_in) per state entry in the reference's
+// state_dict order (oracle/randwire_oracle.param_shapes; kinds as az_net_init_random).
+struct PSpec { size_t n; int kind; int fan_in; };
+std::vector<PSpec> rw_spec(const az_net_desc& d, const std::vector<RwBlock>& rwb) {
+    const int C = d.channels, R = C / 16, HC = d.head_channels, PP = d.pool * d.pool;
+    std::vector<PSpec> s;
+    auto conv = [&](int co, int ci, int k) { s.push_back({(size_t)co * ci * k * k, 0, ci * k * k}); };
+    auto bn = [&](int co) { for (int kd = 2; kd <= 5; ++kd) s.push_back({(size_t)co, kd, 1}); };
+    auto lin = [&](int o, int i) { s.push_back({(size_t)o * i, 0, i}); s.push_back({(size_t)o, 1, i}); };
+    conv(C, d.in_planes, 3); bn(C);
+    for (const RwBlock& b : rwb) {
+        for (int v : b.plan.order)
+            if (!b.plan.preds[v].empty()) { conv(C, (int)b.plan.preds[v].size() * C, 1); bn(C); }
+        for (size_t k = 0; k < b.plan.order.size(); ++k) {
+            conv(C, C, 3); bn(C); conv(C, C, 3); bn(C);
+            lin(R, C); lin(C, R);
+        }
+        if (b.plan.outputs.size() > 1) { conv(C, (int)b.plan.outputs.size() * C, 1); bn(C); }
+    }
+    conv(HC, C, 1); bn(HC); lin(d.action_size, HC * PP);
+    conv(HC, C, 1); bn(HC); lin(d.fc_hidden, HC * PP); lin(1, d.fc_hidden);
+    return s;
+}
+
+int upload_layer(Layer& L, const std::vector<float>& W, const std::vector<float>& b, int N, int K, int taps, int C,
+                 bool split) {
+    L.N = N; L.K = K; L.Kpad = (K + 31) / 32 * 32; L.taps = taps; L.C = C;
+    if (!L.W) { DALLOC(L.W, W.size()); DALLOC(L.b, b.size()); }
+    HIPCHK(hipMemcpy(L.W, W.data(), W.size() * 4, hipMemcpyHostToDevice));
+    HIPCHK(hipMemcpy(L.b, b.data(), b.size() * 4, hipMemcpyHostToDevice));
+    if (split) {
+        std::vector<uint16_t> hi(W.size()), lo(W.size());
+        split_bf16(W.data(), W.size(), hi.data(), lo.data());
+        if (!L.Whi) { DALLOC(L.Whi, W.size()); DALLOC(L.Wlo, W.size()); }
+        HIPCHK(hipMemcpy(L.Whi, hi.data(), hi.size() * 2, hipMemcpyHostToDevice));
+        HIPCHK(hipMemcpy(L.Wlo, lo.data(), lo.size() * 2, hipMemcpyHostToDevice));
+        std::vector<uint16_t> h16(W.size());
+        to_f16(W.data(), W.size(), h16.data());
+        if (!L.Wh16) DALLOC(L.Wh16, W.size());
+        HIPCHK(hipMemcpy(L.Wh16, h16.data(), h16.size() * 2, hipMemcpyHostToDevice));
+        if (taps == 9 && C % 16 == 0) {
+            // chunk-blocked copies of every piece set (v5 / v6 / v7 convs); the fp16 pieces of AZ_PREC_F16X3
+            std::vector<uint16_t> fh(W.size()), fl(W.size());
+            std::vector<float> bx(N), sx(N);
+            pow2_split_rows(W.data(), N, (size_t)9 * C, b.data(), fh.data(), fl.data(), bx.data(), sx.data());
+            if (!L.Wbk_bf) {
+                DALLOC(L.Wbk_bf, W.size()); DALLOC(L.Wbk_h, W.size()); DALLOC(L.Wbk_lo, W.size());
+                DALLOC(L.Wbk_fh, W.size()); DALLOC(L.Wbk_fl, W.size()); DALLOC(L.bx, N); DALLOC(L.sx, N);
+            }
+            HIPCHK(hipMemcpy(L.Wbk_bf, chunk_blocked(hi, N, C).data(), W.size() * 2, hipMemcpyHostToDevice));
+            HIPCHK(hipMemcpy(L.Wbk_h, chunk_blocked(h16, N, C).data(), W.size() * 2, hipMemcpyHostToDevice));
+            HIPCHK(hipMemcpy(L.Wbk_lo, chunk_blocked(lo, N, C).data(), W.size() * 2, hipMemcpyHostToDevice));
+            HIPCHK(hipMemcpy(L.Wbk_fh, chunk_blocked(fh, N, C).data(), W.size() * 2, hipMemcpyHostToDevice));
+            HIPCHK(hipMemcpy(L.Wbk_fl, chunk_blocked(fl, N, C).data(), W.size() * 2, hipMemcpyHostToDevice));
+            HIPCHK(hipMemcpy(L.bx, bx.data(), N * 4, hipMemcpyHostToDevice));
+            HIPCHK(hipMemcpy(L.sx, sx.data(), N * 4, hipMemcpyHostToDevice));
+        }
+    }
+    return 0;
+}
+
+int load_heads(az_net* n, ParamCursor& pc);
+
+int net_load(az_net* n, const float* blob) {
+    const az_net_desc& d = n->d;
+    ParamCursor pc{blob};
+    const int F = d.channels, HC = d.head_channels, PP = d.pool * d.pool;
+    std::vector<float> W, b;
+    const bool split = F % 32 == 0;
+    // k_smallnet weights: every 3x3 layer as [tap][n][c] over 64 channels (input conv zero-padded):
+    // fp16 for k_smallnet_g, bf16 hi / lo parts for k_smallnet_x3 (AZ_PREC_BF16X3), scaled fp16 hi / lo
+    // pieces for k_smallnet_x3<.., 2> (AZ_PREC_F16X3)
+    const bool sm = (d.precision == AZ_PREC_FP16 || d.precision == AZ_PREC_BF16X3 || d.precision == AZ_PREC_F16X3) &&
+                    az_smallnet_supported(d.board_size, F, n->cin_pad, d.pool, HC) && d.blocks <= az_smallnet_max_blocks();
+    // every layer's pieces (fp16, bf16 hi / lo, scaled fp16 hi / lo) are made from its [n][tap][c] rows, then
+    // gathered to [tap][n][c]
+    std::vector<uint16_t> smw, smh, sml, sfh, sfl;
+    std::vector<float> smb, sbx, ssx;
+    auto sm_add = [&](const std::vector<float>& Wl, const std::vector<float>& bl, int cl) {
+        const size_t nw = Wl.size();
+        std::vector<uint16_t> w16(nw), hi(nw), lo(nw), fh(nw), fl(nw);
+        std::vector<float> bx(F), sx(F);
+        to_f16(Wl.data(), nw, w16.data());
+        split_bf16(Wl.data(), nw, hi.data(), lo.data());
+        pow2_split_rows(Wl.data(), F, (size_t)9 * cl, bl.data(), fh.data(), fl.data(), bx.data(), sx.data());
+        smallnet_append(smw, w16, F, cl); smallnet_append(smh, hi, F, cl); smallnet_append(sml, lo, F, cl);
+        smallnet_append(sfh, fh, F, cl); smallnet_append(sfl, fl, F, cl);
+        smb.insert(smb.end(), bl.begin(), bl.end());
+        sbx.insert(sbx.end(), bx.begin(), bx.end());
+        ssx.insert(ssx.end(), sx.begin(), sx.end());
+    };
+    fold_conv(pc, F, d.in_planes, 3, n->cin_pad, d.conv_bias, W, b);
+    if (int r = upload_layer(n->in, W, b, F, 9 * n->cin_pad, 9, n->cin_pad, F % 32 == 0)) return r;  // 16-bit copies: g8 input conv
+    if (n->cin_pad == 16 && d.board_size != 15 && az_conv_g8_supported(d.board_size, d.board_size, F, F) &&
+        az_conv_g8_supported(d.board_size, d.board_size, 32, F)) {
+        std::vector<float> W32((size_t)F * 9 * 32, 0.0f);   // [F][9][32]: channels 16..31 zero
+        for (size_t ot = 0; ot < (size_t)F * 9; ++ot) std::copy(&W[ot * 16], &W[ot * 16] + 16, &W32[ot * 32]);
+        if (int r = upload_layer(n->in32, W32, b, F, 9 * 32, 9, 32, true)) return r;
+    }
+    if (sm) sm_add(W, b, n->cin_pad);
+    n->blk.resize(2 * d.blocks);
+    for (int i = 0; i < 2 * d.blocks; ++i) {
+        fold_conv(pc, F, F, 3, F, d.conv_bias, W, b);
+        if (int r = upload_layer(n->blk[i], W, b, F, 9 * F, 9, F, split)) return r;
+        if (sm) sm_add(W, b, F);
+    }
+    if (sm) {
+        const size_t ne = smw.size();
+        if (!n->sm_W) {
+            DALLOC(n->sm_W, ne); DALLOC(n->sm_Wf, ne); DALLOC(n->sm_Wxh, ne); DALLOC(n->sm_Wxl, ne); DALLOC(n->sm_b, smb.size());
+            DALLOC(n->sm_Wfh, ne); DALLOC(n->sm_Wfl, ne); DALLOC(n->sm_bx, smb.size()); DALLOC(n->sm_sx, smb.size());
+        }
+        HIPCHK(hipMemcpy(n->sm_W, smw.data(), ne * 2, hipMemcpyHostToDevice));
+        HIPCHK(hipMemcpy(n->sm_Wf, frag_major(smw, F).data(), ne * 2, hipMemcpyHostToDevice));
+        HIPCHK(hipMemcpy(n->sm_Wxh, frag_major(smh, F).data(), ne * 2, hipMemcpyHostToDevice));
+        HIPCHK(hipMemcpy(n->sm_Wxl, frag_major(sml, F).data(), ne * 2, hipMemcpyHostToDevice));
+        HIPCHK(hipMemcpy(n->sm_Wfh, frag_major(sfh, F).data(), ne * 2, hipMemcpyHostToDevice));
+        HIPCHK(hipMemcpy(n->sm_Wfl, frag_major(sfl, F).data(), ne * 2, hipMemcpyHostToDevice));
+        HIPCHK(hipMemcpy(n->sm_bx, sbx.data(), sbx.size() * 4, hipMemcpyHostToDevice));
+        HIPCHK(hipMemcpy(n->sm_sx, ssx.data(), ssx.size() * 4, hipMemcpyHostToDevice));
+        HIPCHK(hipMemcpy(n->sm_b, smb.data(), smb.size() * 4, hipMemcpyHostToDevice));
+    }
+    if (int r = load_heads(n, pc)) return r;
+    if (pc.off != n->nparams) return az_fail(AZ_ERR_ARG, "parameter blob size mismatch (%zu vs %zu)", pc.off, n->nparams);
+    n->loaded = true;
+    return 0;
+}
+
+// policy head: 1x1 conv + BN, FC over the flattened (c, y, x) pooled map; value head likewise
+int load_heads(az_net* n, ParamCursor& pc) {
+    const az_net_desc& d = n->d;
+    const int F = d.channels, HC = d.head_channels, PP = d.pool * d.pool;
+    std::vector<float> W, b;
+    fold_conv(pc, HC, F, 1, F, d.conv_bias, W, b);
+    if (int r = upload_layer(n->pconv, W, b, HC, F, 1, F, false)) return r;
+    std::vector<float> hW = W, hb = b;                 // the combined head conv, policy rows first
+    auto fc = [&](int out, int hc, int pp, std::vector<float>& Wt, std::vector<float>& bt) {
+        const float* w = pc.take((size_t)out * hc * pp);
+        const float* bb = pc.take(out);
+        fc_perm(w, out, hc, pp, Wt);
+        bt.assign(bb, bb + out);
+    };
+    fc(d.action_size, HC, PP, W, b);
+    if (int r = upload_layer(n->pfc, W, b, d.action_size, HC * PP, 1, HC * PP, false)) return r;
+    fold_conv(pc, HC, F, 1, F, d.conv_bias, W, b);
+    if (int r = upload_layer(n->vconv, W, b, HC, F, 1, F, false)) return r;
+    hW.insert(hW.end(), W.begin(), W.end());
+    hb.insert(hb.end(), b.begin(), b.end());
+    if (int r = upload_layer(n->hconv, hW, hb, 2 * HC, F, 1, F, false)) return r;
+    fc(d.fc_hidden, HC, PP, W, b);
+    if (int r = upload_layer(n->vfc1, W, b, d.fc_hidden, HC * PP, 1, HC * PP, false)) return r;
+    {
+        const float* w = pc.take(d.fc_hidden);
+        const float* bb = pc.take(1);
+        W.assign(w, w + d.fc_hidden);
+        b.assign(bb, bb + 1);
+        if (int r = upload_layer(n->vfc2, W, b, 1, d.fc_hidden, 1, d.fc_hidden, false)) return r;
+    }
+    // both FC layers as one matrix for k_fc_heads_x3 (wpack::fc_rows)
+    {
+        const int K = HC * PP, A = d.action_size, H = d.fc_hidden;
+        std::vector<float> Wp((size_t)A * K), Wv((size_t)H * K);
+        HIPCHK(hipMemcpy(Wp.data(), n->pfc.W, Wp.size() * 4, hipMemcpyDeviceToHost));
+        HIPCHK(hipMemcpy(Wv.data(), n->vfc1.W, Wv.size() * 4, hipMemcpyDeviceToHost));
+        const FcRows f = fc_rows(Wp.data(), A, Wv.data(), H, K);
+        if (!n->fcx_hi) {
+            DALLOC(n->fcx_hi, f.hi.size()); DALLOC(n->fcx_lo, f.lo.size());
+            DALLOC(n->fcf_hi, f.fh.size()); DALLOC(n->fcf_lo, f.fl.size()); DALLOC(n->fcf_rs, f.rs.size());
+        }
+        HIPCHK(hipMemcpy(n->fcx_hi, f.hi.data(), f.hi.size() * 2, hipMemcpyHostToDevice));
+        HIPCHK(hipMemcpy(n->fcx_lo, f.lo.data(), f.lo.size() * 2, hipMemcpyHostToDevice));
+        HIPCHK(hipMemcpy(n->fcf_hi, f.fh.data(), f.fh.size() * 2, hipMemcpyHostToDevice));
+        HIPCHK(hipMemcpy(n->fcf_lo, f.fl.data(), f.fl.size() * 2, hipMemcpyHostToDevice));
+        HIPCHK(hipMemcpy(n->fcf_rs, f.rs.data(), f.rs.size() * 4, hipMemcpyHostToDevice));
+    }
+    return 0;
+}
+
+// DDW-RandWire blob (rw_spec order): input conv, per block the routers (nodes() order, in-degree
+// > 0), the nodes' residual blocks incl. SE, the output router; then the heads.
+int net_load_rw(az_net* n, const float* blob) {
+    const az_net_desc& d = n->d;
+    const int F = d.channels, R = F / 16;
+    ParamCursor pc{blob};
+    std::vector<float> W, b;
+    fold_conv(pc, F, d.in_planes, 3, n->cin_pad, false, W, b);
+    if (int r = upload_layer(n->in, W, b, F, 9 * n->cin_pad, 9, n->cin_pad, false)) return r;
+    auto raw = [&](float** dst, size_t cnt) -> int {
+        if (!*dst) DALLOC(*dst, cnt);
+        HIPCHK(hipMemcpy(*dst, pc.take(cnt), cnt * 4, hipMemcpyHostToDevice));
+        return 0;
+    };
+    for (RwBlock& blk : n->rwb) {
+        const azrw::Plan& pl = blk.plan;
+        for (int v : pl.order) {
+            const int deg = (int)pl.preds[v].size();
+            if (!deg) continue;
+            fold_conv(pc, F, deg * F, 1, deg * F, false, W, b);
+            if (int r = upload_layer(blk.node[v].router, W, b, F, deg * F, 1, deg * F, false)) return r;
+        }
+        for (int v : pl.order) {
+            RwNode& nd = blk.node[v];
+            const bool h16 = F % 32 == 0;   // 16-bit weight copies: the fp16 node convs (conv3x3_v4)
+            fold_conv(pc, F, F, 3, F, false, W, b);
+            if (int r = upload_layer(nd.c1, W, b, F, 9 * F, 9, F, h16)) return r;
+            fold_conv(pc, F, F, 3, F, false, W, b);
+            if (int r = upload_layer(nd.c2, W, b, F, 9 * F, 9, F, h16)) return r;
+            if (int r = raw(&nd.w1, (size_t)R * F)) return r;
+            if (int r = raw(&nd.b1, R)) return r;
+            if (int r = raw(&nd.w2, (size_t)F * R)) return r;
+            if (int r = raw(&nd.b2, F)) return r;
+        }
+        const int no = (int)pl.outputs.size();
+        if (no > 1) {
+            fold_conv(pc, F, no * F, 1, no * F, false, W, b);
+            if (int r = upload_layer(blk.out_router, W, b, F, no * F, 1, no * F, false)) return r;
+        }
+    }
+    if (int r = load_heads(n, pc)) return r;
+    if (pc.off != n->nparams) return az_fail(AZ_ERR_ARG, "parameter blob size mismatch (%zu vs %zu)", pc.off, n->nparams);
+    n->loaded = true;
+    return 0;
+}
+
+}  // namespace
+
+size_t net_blob_params(const az_net* n) {
+    if (!n->rw) return count_params(n->d);
+    size_t total = 0;
+    for (const PSpec& ps : rw_spec(n->d, n->rwb)) total += ps.n;
+    return total;
+}
+
+// ---- net internals for dist.hip (engine_internal.h), C++ linkage
+int net_weight_buffers(az_net* n, std::vector<std::pair<void*, size_t>>& out) {
+    if (n->wbufs.empty()) {
+        // never loaded: a load of zero weights allocates (and records) every weight buffer, which a
+        // broadcast then overwrites (host work once per net, no device traffic beyond the uploads)
+        std::vector<float> zero(n->nparams, 0.0f);
+        WeightRegistry reg(&n->wbufs);
+        if (int r = n->rw ? net_load_rw(n, zero.data()) : net_load(n, zero.data())) return r;
+        HIPCHK(hipDeviceSynchronize());
+        n->loaded = false;
+    }
+    out = n->wbufs;
+    return 0;
+}
+const std::vector<float>& net_host_blob(az_net* n) { return n->host_blob; }
+size_t net_param_count(az_net* n) { return n->nparams; }
+az_engine* net_engine(az_net* n) { return n->e; }
+std::mutex& net_mutex(az_net* n) { return n->mu; }
+void net_adopt_blob(az_net* n, const float* blob) {
+    n->host_blob.assign(blob, blob + n->nparams);
+    n->loaded = true;
+}
+
+extern "C" {
+
+int az_net_num_params(az_net* n, size_t* count) {
+    if (!n || !count) return az_fail(AZ_ERR_ARG, "null argument");
+    *count = n->nparams;
+    return 0;
+}
+
+int az_net_load_weights(az_net* n, const float* blob, size_t count) {
+    if (!n || !blob) return az_fail(AZ_ERR_ARG, "null argument");
+    if (count != n->nparams) return az_fail(AZ_ERR_ARG, "expected %zu parameters, got %zu", n->nparams, count);
+    std::lock_guard<std::mutex> lk(n->mu);
+    HIPCHK(hipSetDevice(n->e->device));
+    {
+        // the first load allocates the weight buffers: record them (net_weight_buffers)
+        WeightRegistry reg(n->wbufs.empty() ? &n->wbufs : nullptr);
+        if (int r = n->rw ? net_load_rw(n, blob) : net_load(n, blob)) return r;
+    }
+    HIPCHK(hipDeviceSynchronize());   // null-stream uploads done before the non-blocking stream reads them
+    n->host_blob.assign(blob, blob + count);
+    return 0;
+}
+
+int az_net_get_weights(az_net* n, float* blob, size_t count) {
+    if (!n || !blob) return az_fail(AZ_ERR_ARG, "null argument");
+    std::lock_guard<std::mutex> lk(n->mu);
+    if (!n->loaded) return az_fail(AZ_ERR_STATE, "weights not loaded");
+    if (count != n->nparams) return az_fail(AZ_ERR_ARG, "expected %zu parameters, got %zu", n->nparams, count);
+    std::copy(n->host_blob.begin(), n->host_blob.end(), blob);
+    return 0;
+}
+
+// Counter-based init; tests/nn_weights.py restates it in numpy (same fp32 ops).
+int az_net_init_random(az_net* n, uint64_t seed) {
+    if (!n) return az_fail(AZ_ERR_ARG, "null net");
+    const az_net_desc& d = n->d;
+    std::vector<float> blob(n->nparams);
+    size_t off = 0;
+    int tensor = 0;
+    auto fill = [&](size_t cnt, int kind, int fan_in) {
+        // kind: 0 weight U(-1,1)/sqrt(fan_in); 1 bias U(-1,1)/sqrt(fan_in); 2 bn gamma 1+0.1u;
+        //       3 bn beta 0.1u; 4 bn mean 0.1u; 5 bn var 1+0.25(u+1)
+        const float bound = 1.0f / std::sqrt((float)fan_in);
+        for (size_t i = 0; i < cnt; ++i) {
+            const uint64_t r = splitmix64(seed ^ ((uint64_t)tensor << 40) ^ (uint64_t)i);
+            const float u = (float)(int32_t)(r >> 40) * (1.0f / 8388608.0f) - 1.0f;
+            float v;
+            switch (kind) {
+                case 0: case 1: v = u * bound; break;
+                case 2: v = 1.0f + 0.1f * u; break;
+                case 3: case 4: v = 0.1f * u; break;
+                default: v = 1.0f + 0.25f * (u + 1.0f); break;
+            }
+            blob[off + i] = v;
+        }
+        off += cnt;
+        ++tensor;
+    };
+    if (n->rw) {
+        for (const PSpec& ps : rw_spec(d, n->rwb)) fill(ps.n, ps.kind, ps.fan_in);
+        if (off != n->nparams) return az_fail(AZ_ERR_STATE, "init size mismatch");
+        return az_net_load_weights(n, blob.data(), blob.size());
+    }
+    const int F = d.channels, HC = d.head_channels, PP = d.pool * d.pool;
+    auto conv = [&](int co, int ci, int k) {
+        fill((size_t)co * ci * k * k, 0, ci * k * k);
+        if (d.conv_bias) fill(co, 1, ci * k * k);
+        fill(co, 2, 1); fill(co, 3, 1); fill(co, 4, 1); fill(co, 5, 1);
+    };
+    conv(F, d.in_planes, 3);
+    for (int i = 0; i < d.blocks; ++i) { conv(F, F, 3); conv(F, F, 3); }
+    conv(HC, F, 1);
+    fill((size_t)d.action_size * HC * PP, 0, HC * PP); fill(d.action_size, 1, HC * PP);
+    conv(HC, F, 1);
+    fill((size_t)d.fc_hidden * HC * PP, 0, HC * PP); fill(d.fc_hidden, 1, HC * PP);
+    fill(d.fc_hidden, 0, d.fc_hidden); fill(1, 1, d.fc_hidden);
+    if (off != n->nparams) return az_fail(AZ_ERR_STATE, "init size mismatch");
+    return az_net_load_weights(n, blob.data(), blob.size());
+}
+
+}  // extern "C"

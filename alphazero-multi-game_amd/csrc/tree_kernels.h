@@ -1,0 +1,30 @@
+// tree_kernels.h -- launch interface of the search kernels (tree_kernels.hip): the launchers and
+// the kernels that the host launches directly.  The one declaration of each, included by
+// tree_kernels.hip and by every file that calls them.  The data layout is tree.h.
+#pragma once
+#include <hip/hip_runtime.h>
+
+#include "tree.h"
+
+void az_launch_select(const TreeDev* t, int NA, int G, int mode, hipStream_t st);
+void az_launch_expand_select(const TreeDev* ts, const int* eval_slot, int eval_identity, int NA, int G, hipStream_t st);
+__global__ void k_scan(const TreeDev* __restrict__ tp);
+__global__ void k_expand_backup(const TreeDev* __restrict__ tp, int mode);
+__global__ void k_select_action(const TreeDev* __restrict__ tp, int training, float temperature, const float* temps, int* actions, float* values, float* probs,
+                                int* child_actions, int* nchild);
+__global__ void k_apply(TreeDev t, const int* actions, int* terminal, int* result, int* rexp);
+__global__ void k_compact(TreeDev t, Nodes dst, int* src_of);
+__global__ void k_leaf_moves(TreeDev t, int* moves, int* len);
+__global__ void k_prune(TreeDev t, Nodes dst, int* src_of, int thr_all, const int* thr_g, long long* pruned);
+__global__ void k_noise(TreeDev t, const float* noise, const uint8_t* mask, float eps);
+__global__ void k_new_games(TreeDev t, const int* games, const int* seed_ids, int n, uint32_t eval_seed);
+__global__ void k_init_slots(TreeDev t, Nodes other);
+__global__ void k_tt_clear(TreeDev t, const int* games, int n);
+__global__ void k_root_nchild(TreeDev t, int* out);
+__global__ void k_root_children(TreeDev t, int g, int* act, int* N, int* VL, float* W, float* P, int* n, int* rootinfo,
+                                float* rootW);
+// replay dataset (dataset.hip)
+__global__ void k_dataset_extract(DatasetDev d, TreeDev t);
+__global__ void k_dataset_gather(const float* states, const float* policy, const int* plen, const float* value, int row,
+                                 int NA, const long long* idx, int n, float* ostates, float* opolicy, int* oplen,
+                                 float* ovalue);

@@ -21,7 +21,7 @@
 #include <hip/hip_runtime.h>
 #include <float.h>
 #include <limits.h>
-#include "tree.h"
+#include "tree_kernels.h"
 #include "leaf_planes.h"
 
 namespace {
@@ -938,7 +938,7 @@ __device__ __forceinline__ void select_game(const TreeDev& t, int mode, const Ro
 
 template <int IT>
 __global__ __launch_bounds__(64) void k_select(const TreeDev* __restrict__ tp, int mode) {
-    const TreeDev& t = *tp;                               // device-resident (tree_dev, engine.hip): an 8-byte kernarg
+    const TreeDev& t = *tp;                               // device-resident (tree_dev, search_host.hip): an 8-byte kernarg
     __shared__ SelLds SL;
     __shared__ GoLds gl;
     select_game<IT>(t, mode, nullptr, SL, gl);

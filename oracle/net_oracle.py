@@ -58,7 +58,7 @@ def param_shapes(desc):
 
 
 def init_blob(desc, seed):
-    """Numpy restatement of az_net_init_random (engine.hip), bit-identical."""
+    """Numpy restatement of az_net_init_random (net_load.hip), bit-identical."""
     parts = []
     seed = np.uint64(seed)
     for t, (_, shape, kind, fan_in) in enumerate(param_shapes(desc)):

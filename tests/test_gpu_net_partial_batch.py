@@ -1,6 +1,6 @@
-"""The compacted network batch of the search (engine.hip search_step: k_scan writes eval_slot /
+"""The compacted network batch of the search (search_host.hip search_step: k_scan writes eval_slot /
 eval_games / n_eval and the net runs with LeafRecs.identity = 0) on each of the three input stages
-that consume the batch map (engine.hip net_input_path):
+that consume the batch map (net_host.hip net_input_path):
   NET_IN_SMALL  k_smallnet_g / k_smallnet_x3 read the leaf records through gidx
   NET_IN_G8     az_launch_rec_to_g8(rec, gidx, ...) -- 15x15 (NG = 2), the other boards through in32
                 (NG = 4), Go records

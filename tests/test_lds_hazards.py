@@ -11,7 +11,8 @@ import pytest
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 BUILD = os.path.join(ROOT, "alphazero-multi-game_amd", "build")
-OBJS = ["conv_v7.o", "conv_bf16.o", "smallnet.o", "net_kernels.o", "tree_kernels.o", "engine.o"]
+OBJS = ["conv_v7.o", "conv_bf16.o", "smallnet.o", "net_kernels.o", "tree_kernels.o", "engine.o", "net_host.o", "net_load.o",
+        "search_host.o", "selfplay.o"]
 
 
 @pytest.mark.parametrize("obj", OBJS)

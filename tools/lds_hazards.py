@@ -24,7 +24,8 @@ import tempfile
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 LLVM = "/opt/rocm/lib/llvm/bin"
-DEFAULT = ["conv_v7.o", "conv_bf16.o", "smallnet.o", "net_kernels.o", "tree_kernels.o", "engine.o", "dataset.o"]
+DEFAULT = ["conv_v7.o", "conv_bf16.o", "smallnet.o", "net_kernels.o", "tree_kernels.o", "engine.o", "net_host.o", "net_load.o",
+           "search_host.o", "selfplay.o", "dataset.o"]
 BRANCHES = {"s_branch", "s_cbranch_scc0", "s_cbranch_scc1", "s_cbranch_vccz", "s_cbranch_vccnz",
             "s_cbranch_execz", "s_cbranch_execnz"}
 REG = re.compile(r"\bv\[(\d+):(\d+)\]|\bv(\d+)\b")

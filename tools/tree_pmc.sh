@@ -5,7 +5,7 @@
 # kernel timing on, so its JSON line carries the kernels' algorithmic bytes), then FETCH_SIZE and
 # WRITE_SIZE in separate passes.  Rounds 2-3 had to pass --kernel-timing 0 there: a search that
 # recorded HIP events hung under counter collection (tools/pmc_hang_probe2.sh); since round 4 the
-# timing uses device clock-stamp kernels instead of events (engine.hip ProfClock), and KT (default 1)
+# timing uses device clock-stamp kernels instead of events (engine_internal.h ProfClock), and KT (default 1)
 # keeps the bench's timing on in the counter passes too.
 # --kernel-include-regex is not used (round 2: SIGSEGV in the profiler's launch hook).
 set -o pipefail
