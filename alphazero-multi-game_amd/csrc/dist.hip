@@ -261,6 +261,9 @@ int az_diag_net_copy_weights(az_net* dst, az_net* src) {
         if (a[i].second != b[i].second) return az_fail(AZ_ERR_ARG, "the nets differ (buffer %zu)", i);
         HIPCHK(hipMemcpy(a[i].first, b[i].first, a[i].second, hipMemcpyDeviceToDevice));
     }
+    // device-to-device copies on the null stream need not be done when hipMemcpy returns, and the forwards
+    // run on the engine's non-blocking stream, which does not wait for them (as az_net_load_weights)
+    HIPCHK(hipDeviceSynchronize());
     const std::vector<float> blob = net_host_blob(src);
     net_adopt_blob(dst, blob.data());
     return 0;

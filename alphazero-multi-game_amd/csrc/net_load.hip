@@ -111,9 +111,11 @@ int net_load(az_net* n, const float* blob) {
     const bool split = F % 32 == 0;
     // k_smallnet weights: every 3x3 layer as [tap][n][c] over 64 channels (input conv zero-padded):
     // fp16 for k_smallnet_g, bf16 hi / lo parts for k_smallnet_x3 (AZ_PREC_BF16X3), scaled fp16 hi / lo
-    // pieces for k_smallnet_x3<.., 2> (AZ_PREC_F16X3)
-    const bool sm = (d.precision == AZ_PREC_FP16 || d.precision == AZ_PREC_BF16X3 || d.precision == AZ_PREC_F16X3) &&
-                    az_smallnet_supported(d.board_size, F, n->cin_pad, d.pool, HC) && d.blocks <= az_smallnet_max_blocks();
+    // pieces for k_smallnet_x3<.., 2> (AZ_PREC_F16X3).  Decided by the shape alone, like every other
+    // piece set: az_net_set_precision only switches the dispatch, so a load packs what any precision the
+    // shape accepts will read, and the buffer list recorded at the first load (net_weight_buffers) is
+    // the same whatever precision the net had then
+    const bool sm = az_smallnet_supported(d.board_size, F, n->cin_pad, d.pool, HC) && d.blocks <= az_smallnet_max_blocks();
     // every layer's pieces (fp16, bf16 hi / lo, scaled fp16 hi / lo) are made from its [n][tap][c] rows, then
     // gathered to [tap][n][c]
     std::vector<uint16_t> smw, smh, sml, sfh, sfl;

@@ -126,6 +126,11 @@ int az_net_init_random(az_net* n, uint64_t seed);
 /* The loaded weights as the canonical blob (count = az_net_num_params): what rank 0 broadcasts
  * to the other ranks; AZ_ERR_STATE before any load/init. */
 int az_net_get_weights(az_net* n, float* blob, size_t count);
+/* Switch the arithmetic of a net in place.  Every load packs every weight set the net's shape can
+ * run, so the outputs, az_net_trunk_kernel and az_net_get_weights of a net depend only on its
+ * description, its current precision and the last blob loaded, never on the precisions it had before
+ * (tests/test_gpu_net_lifecycle.py).  A precision the shape has no kernel for is refused with
+ * AZ_ERR_ARG and the net stays as it was. */
 int az_net_set_precision(az_net* n, int precision);
 /* planes: host fp32 NCHW [B][in_planes][H][W].  logits [B][A] raw, value [B] (tanh). */
 int az_net_forward(az_net* n, const float* planes, int B, float* logits, float* value);

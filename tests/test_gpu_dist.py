@@ -53,8 +53,10 @@ def test_gpu_broadcast_receiver_side_matches_root(engine, shape):
     import az_amd
     from az_amd import _lib
     bs, F, blocks, B = shape
-    # created as fp16 nets (the bench's nets): every piece set packed at load, the 64-filter fused
-    # kernel's included (an F32-created 64-filter net packs none of them)
+    # created as fp16 nets (the bench's nets).  Every piece set is packed at load whatever the
+    # precision then, the 64-filter fused kernel's included; nets created at other precisions (F32
+    # among them), and src / dst pairs of different histories, are the broadcast history of
+    # tests/test_gpu_net_lifecycle.py
     desc = az_amd.gomoku_net_desc(board_size=bs, channels=F, blocks=blocks, precision=az_amd.AZ_PREC_FP16, max_batch=B)
     src = az_amd.HipNeuralNetwork(engine, desc)
     dst = az_amd.HipNeuralNetwork(engine, az_amd.gomoku_net_desc(board_size=bs, channels=F, blocks=blocks,

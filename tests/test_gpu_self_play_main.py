@@ -122,3 +122,59 @@ def test_gpu_self_play_binary_with_net_matches_in_process(tmp_path):
     assert (md["num_games_requested"], md["num_games_completed"]) == (n, n)
     assert md["total_moves"] == sum(len(t.moves) for t in twins)
     assert md["precision"] == "f32" and md["fp16_used"] is False and md["world"] == 1
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("precision", [None, "fp16", "bf16x3"], ids=["default", "fp16", "bf16x3"])
+def test_gpu_self_play_binary_c2_shape_net_matches_in_process(tmp_path, precision):
+    """The binary on the C2 net's shape class (15x15, 64 filters: the fused k_smallnet kernels): it creates
+    its random-init net at f32 and switches it to the run's precision afterwards -- with no --precision
+    that is f16x3, the fp32-faithful fp16 pieces -- so the weight sets of the fused kernels must be on the
+    device whatever precision the net was loaded at (tests/test_gpu_net_lifecycle.py).  Its records
+    equal, move for move, those of the same run in-process with a net CREATED at that precision."""
+    import az_amd
+    n, slots, bs, sims, seed, max_moves = 2, 2, 15, 8, 7, 3
+    want = precision or "f16x3"
+    out = tmp_path / "games"
+    cmd = [BIN, "--game", "gomoku", "--size", str(bs), "--num-games", str(n), "--batch-size", str(slots),
+           "--simulations", str(sims), "--max-moves", str(max_moves), "--net-blocks", "2", "--net-channels", "64",
+           "--seed", str(seed), "--output-dir", str(out), "--threads", "4"]
+    if precision:
+        cmd += ["--precision", precision]
+    r = subprocess.run(cmd, capture_output=True, text=True, timeout=240)
+    assert r.returncode == 0, r.stdout + r.stderr
+    md = [json.load(open(f)) for f in glob.glob(str(out / "metadata_*.json"))]
+    assert len(md) == 1
+    md = md[0]
+    assert md["precision"] == want
+    assert (md["num_games_requested"], md["num_games_completed"]) == (n, n)
+    prec = {"f16x3": az_amd.AZ_PREC_F16X3, "fp16": az_amd.AZ_PREC_FP16, "bf16x3": az_amd.AZ_PREC_BF16X3}[want]
+    eng = az_amd.Engine(0)
+    desc = az_amd.gomoku_net_desc(board_size=bs, channels=64, blocks=2, precision=prec, max_batch=slots)
+    net = az_amd.HipNeuralNetwork(eng, desc)
+    assert net.trunk_kernel().startswith("k_smallnet_g<15," if want == "fp16" else "k_smallnet_x3<15,")
+    net.init_random(seed)
+    mgr = az_amd.SelfPlayManager(eng, net=net, numGames=slots, numSimulations=sims, board_size=bs, fpu_reduction=0.1,
+                                 use_dirichlet_each_search=True, noise_seed=42, noise_seed_stride=1)
+    try:
+        twins = mgr.generateGames(totalGames=n, max_moves=max_moves)
+    finally:
+        mgr.mcts.close()
+        net.close()
+    assert [t.game_id for t in twins] == list(range(n))
+    for g, twin in enumerate(twins):
+        files = glob.glob(str(out / f"{g:03d}_*.json"))
+        assert len(files) == 1, g
+        rec = json.load(open(files[0]))
+        assert rec["board_size"] == bs and len(rec["moves"]) == len(twin.moves) == max_moves, g
+        for ply, (mv, tm) in enumerate(zip(rec["moves"], twin.moves)):
+            assert mv["action"] == tm.action, (g, ply)
+            # JSON keeps no NaN payload (null): the T = 0 NaN entries are compared as NaNs
+            tp = np.asarray(tm.policy, np.float32)
+            assert len(mv["policy"]) == len(tp) and all((p is None) == bool(np.isnan(t)) for p, t in zip(mv["policy"], tp)), \
+                (g, ply)
+            assert _bits([0.0 if p is None else p for p in mv["policy"]]) == \
+                _bits(np.where(np.isnan(tp), np.float32(0.0), tp)), (g, ply)
+            assert _bits([mv["value"]])[0] == _bits([tm.value])[0], (g, ply)
+        assert rec["result"] == twin.result, g
+    assert md["total_moves"] == sum(len(t.moves) for t in twins)
