@@ -19,9 +19,9 @@ from dataclasses import dataclass, field
 import numpy as np
 
 from ._lib import (AZ_EVAL_CALLBACK, AZ_EVAL_HASH, AZ_EVAL_NET, AZ_EVAL_RANDOM, AZ_EVAL_UNIFORM, EVAL_FN, AZ_PREC_BF16, AZ_PREC_BF16X3, AZ_PREC_F16X3, AZ_PREC_F32, AZ_PREC_FP16, AzError,
-                   GAME_SINK, PROGRESS_FN, MoveRec as _lib_MoveRec, NetDesc, SearchCfg, SelfPlayCfg, check, lib)
+                   ARENA_SINK, ArenaCfg, ArenaSummary, GAME_SINK, PROGRESS_FN, MoveRec as _lib_MoveRec, NetDesc, SearchCfg, SelfPlayCfg, check, lib)
 
-__all__ = ["Engine", "HipNeuralNetwork", "ParallelMCTS", "SelfPlayManager", "GameRecord", "MoveData", "AzError",
+__all__ = ["Engine", "HipNeuralNetwork", "ParallelMCTS", "SelfPlayManager", "Arena", "ArenaGameRecord", "EloRating", "GameRecord", "MoveData", "AzError",
            "Dataset", "TrainingExample", "GAME_GOMOKU", "GAME_GO",
            "AZ_PREC_F32", "AZ_PREC_BF16X3", "AZ_PREC_F16X3", "AZ_PREC_BF16", "AZ_PREC_FP16", "AZ_EVAL_NET", "AZ_EVAL_HASH", "AZ_EVAL_RANDOM", "AZ_EVAL_UNIFORM", "AZ_EVAL_CALLBACK",
            "gomoku_net_desc"]
@@ -246,9 +246,31 @@ class ParallelMCTS:
             self._cb = EVAL_FN(_eval)
             check(lib().az_search_set_evaluator(self.h, self._cb, None))
 
-    def newGames(self, games=None):
-        games = np.arange(self.G, dtype=np.int32) if games is None else np.asarray(games, np.int32)
-        check(lib().az_search_new_games(self.h, _ip(games), games.size))
+    def newGames(self, games=None, ids=None):
+        """Start fresh games in the listed slots (all by default).  ids: each game's stream id for its
+        evaluator / noise seeds (az_search_new_games_ids; default the slot index)."""
+        games = np.arange(self.G, dtype=np.int32) if games is None else np.ascontiguousarray(games, np.int32)
+        if ids is None:
+            check(lib().az_search_new_games(self.h, _ip(games), games.size))
+        else:
+            ids = np.ascontiguousarray(ids, np.int32)
+            assert ids.size == games.size
+            check(lib().az_search_new_games_ids(self.h, games.ctypes.data, ids.ctypes.data, games.size))
+
+    def setNet(self, net):
+        """ParallelMCTS::setNeuralNetwork on every slot (az_search_set_net); ends per-slot nets."""
+        check(lib().az_search_set_net(self.h, net.h))
+        self.net, self._slot_nets = net, None
+
+    def setSlotNets(self, nets, slot_net):
+        """Slot g is evaluated by nets[slot_net[g]] from the next search on (az_search_set_slot_nets):
+        up to 4 nets of the handle's shape, each with max_batch >= its number of slots."""
+        sn = np.ascontiguousarray(slot_net, dtype=np.uint8).reshape(-1)
+        if sn.size != self.G:
+            raise ValueError(f"slot_net holds {sn.size} entries, the handle has {self.G} slots")
+        arr = (ctypes.c_void_p * max(1, len(nets)))(*[n.h.value for n in nets])
+        check(lib().az_search_set_slot_nets(self.h, arr, len(nets), sn.ctypes.data_as(ctypes.POINTER(ctypes.c_uint8))))
+        self._slot_nets = list(nets)      # kept alive with the handle
 
     def addDirichletNoise(self, alpha=0.03, epsilon=0.25, mask=None):
         if mask is None:
@@ -258,8 +280,14 @@ class ParallelMCTS:
             check(lib().az_search_add_noise_masked(self.h, alpha, epsilon,
                                                    m.ctypes.data_as(ctypes.POINTER(ctypes.c_uint8))))
 
-    def search(self):
-        check(lib().az_search_run(self.h))
+    def search(self, mask=None):
+        """One search of every playing game; mask [G]: only of the games it marks (az_search_run_masked),
+        the other trees untouched."""
+        if mask is None:
+            check(lib().az_search_run(self.h))
+        else:
+            m = np.ascontiguousarray(mask, dtype=np.uint8).reshape(self.G)
+            check(lib().az_search_run_masked(self.h, m.ctypes.data))
 
     def runSingleSimulation(self, n=1):
         """ParallelMCTS::runSingleSimulation (parallel_mcts.cpp:276-380), n times, every game."""
@@ -285,8 +313,9 @@ class ParallelMCTS:
                                             int(bool(useBatchInference)), _ip(lg), int(lg.size), ctypes.byref(a)))
         return a.value
 
-    def select(self, is_training=True, temperature=1.0):
-        """(actions [G], root values [G], probs [G][A] child order, child actions [G][A], n_children [G])."""
+    def select(self, is_training=True, temperature=1.0, mask=None):
+        """(actions [G], root values [G], probs [G][A] child order, child actions [G][A], n_children [G]).
+        mask [G]: the games outside it report no action (-1, Go: AZ_ACTION_NONE) and no children."""
         G, A = self.G, self.A
         act = np.zeros(G, np.int32)
         val = np.zeros(G, np.float32)
@@ -295,6 +324,10 @@ class ParallelMCTS:
         nch = np.zeros(G, np.int32)
         check(lib().az_search_select(self.h, int(is_training), temperature, _ip(act), _fp(val), _fp(probs), _ip(cact),
                                      _ip(nch)))
+        if mask is not None:
+            off = ~np.asarray(mask, bool).reshape(G)
+            act[off] = self.none
+            nch[off] = 0
         return act, val, probs, cact, nch
 
     def selectAction(self, isTraining=False, temperature=1.0):
@@ -412,7 +445,8 @@ class ParallelMCTS:
 
     def close(self):
         if self.h:
-            lib().az_search_destroy(self.h)
+            if not getattr(self, "_borrowed", False):
+                lib().az_search_destroy(self.h)
             self.h = None
 
 
@@ -521,6 +555,119 @@ class SelfPlayManager:
                 m.addDirichletNoise(self.dirichletAlpha, self.dirichletEpsilon)
             move += 1
         return records
+
+
+# ---------------------------------------------------------------------------- Arena
+class EloRating:
+    """python/alphazero/utils/elo.py EloRating (ratings in doubles through az_elo_update)."""
+
+    def __init__(self, initial_rating=1500.0, k_factor=32.0):
+        self.initial_rating, self.k_factor = float(initial_rating), float(k_factor)
+        self.ratings = {}
+
+    def getRating(self, player_id):
+        return self.ratings.get(player_id, self.initial_rating)
+
+    def addGameResult(self, player_id, opponent_id, score):
+        a, b = ctypes.c_double(self.getRating(player_id)), ctypes.c_double(self.getRating(opponent_id))
+        lib().az_elo_update(ctypes.byref(a), ctypes.byref(b), float(score), self.k_factor)
+        self.ratings[player_id], self.ratings[opponent_id] = a.value, b.value
+        return a.value
+
+
+@dataclass
+class ArenaGameRecord:
+    """One finished arena game: moves as MoveData (root value and child-order visit distribution of the
+    mover's tree), movers[i] 0 (net A) or 1 (net B), result a GameResult (0: cut at max_moves), score_a."""
+    game_id: int
+    board_size: int
+    a_is_player1: bool
+    moves: list
+    movers: list
+    result: int
+    score_a: float
+    evals_a: int = 0
+    evals_b: int = 0
+
+
+class Arena:
+    """Net A against net B on `tables` boards in lock step (az_arena_*): the game loop of the reference's
+    python/scripts/evaluate.py on one search handle whose slots 2i / 2i + 1 are A's / B's tree of table i."""
+
+    def __init__(self, engine, net_a, net_b, tables, board_size=15, num_simulations=800, swap_colors=False,
+                 temperature=0.1, sample_moves=0, noise_alpha=0.03, noise_eps=0.0, game=0, c_puct=1.5,
+                 fpu_reduction=0.0, virtual_loss=3, zobrist_seed=12345, noise_seed=42, noise_seed_stride=1, tt_log2=20,
+                 node_capacity=0, prior_ring=0):
+        self.tables, self.engine, self.nets = int(tables), engine, (net_a, net_b)
+        self.cfg = SearchCfg(self.tables, board_size, num_simulations, c_puct, fpu_reduction, virtual_loss, AZ_EVAL_NET,
+                             7, zobrist_seed, noise_seed, noise_seed_stride, 0, noise_alpha, noise_eps, tt_log2,
+                             node_capacity, prior_ring, game)
+        self.acfg = ArenaCfg(int(bool(swap_colors)), temperature, int(sample_moves), noise_alpha, noise_eps)
+        h = ctypes.c_void_p()
+        check(lib().az_arena_create(engine.h, net_a.h, net_b.h, ctypes.byref(self.cfg), ctypes.byref(self.acfg),
+                                    ctypes.byref(h)))
+        self.h = h
+        # the underlying handle as a ParallelMCTS view (rootChildren, counters, the evaluation log); not owned
+        m = ParallelMCTS.__new__(ParallelMCTS)
+        m.G, m.bs, m.game = 2 * self.tables, board_size, game
+        m.A = board_size * board_size + (1 if game == AZ_GAME_GO else 0)
+        m.none = AZ_ACTION_NONE if game == AZ_GAME_GO else -1
+        m.h = ctypes.c_void_p(lib().az_arena_search(self.h))
+        m.engine, m.net, m._cb, m._borrowed, m.cfg = engine, net_a, None, True, self.cfg
+        self.search = m
+        self.progressCallback = None
+
+    def step(self):
+        """One ply on every live table; returns the moves played."""
+        n = ctypes.c_int64(0)
+        check(lib().az_arena_step(self.h, ctypes.byref(n)))
+        return n.value
+
+    def tableGames(self):
+        """The game id each table plays now (-1: idle)."""
+        ids = np.zeros(self.tables, np.int32)
+        check(lib().az_arena_table_games(self.h, _ip(ids)))
+        return ids.tolist()
+
+    def run(self, total_games, max_moves=0, abort=None):
+        """total_games games from fresh tables; returns their ArenaGameRecords by game id.
+        progressCallback(game_id, ply, total_games, total_moves), when set, is called for every move after
+        it is chosen and before it is applied."""
+        recs = [None] * int(total_games)
+
+        def sink(_user, gp):
+            g = gp.contents
+            moves = []
+            for i in range(g.n_moves):
+                mv = g.moves[i]
+                k = mv.n_children
+                moves.append(MoveData(int(mv.action), mv.policy[:k], float(mv.value), int(mv.thinking_time_ms),
+                                      mv.child_actions[:k]))
+            recs[g.game_id] = ArenaGameRecord(int(g.game_id), int(g.board_size), bool(g.a_is_player1), moves,
+                                              [int(g.mover[i]) for i in range(g.n_moves)], int(g.result),
+                                              float(g.score_a), int(g.evals_a), int(g.evals_b))
+
+        def progress(_user, gid, move, tg, tm):
+            if self.progressCallback:
+                self.progressCallback(int(gid), int(move), int(tg), int(tm))
+
+        flag = ctypes.c_int(0) if abort is None else abort
+        cb_sink, cb_prog = ARENA_SINK(sink), PROGRESS_FN(progress)
+        check(lib().az_arena_run(self.h, int(total_games), int(max_moves), cb_sink, cb_prog, None, ctypes.byref(flag)))
+        return recs
+
+    def summary(self):
+        """dict(games, wins_a, wins_b, draws, moves, evals_a, evals_b, elo_a, elo_b) of the games finished since
+        the last run() began."""
+        out = ArenaSummary()
+        check(lib().az_arena_summary_read(self.h, ctypes.byref(out)))
+        return {n: getattr(out, n) for n, _ in ArenaSummary._fields_}
+
+    def close(self):
+        if self.h:
+            self.search.close()
+            lib().az_arena_destroy(self.h)
+            self.h = None
 
 
 # ---------------------------------------------------------------------------- Dataset (row f3)

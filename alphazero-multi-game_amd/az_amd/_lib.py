@@ -47,6 +47,23 @@ class MoveRec(ctypes.Structure):
                 ("child_actions", P(c_int)), ("thinking_time_ms", c_int64)]
 
 
+class ArenaCfg(ctypes.Structure):
+    _fields_ = [("swap_colors", c_int), ("temperature", c_float), ("sample_moves", c_int), ("noise_alpha", c_float),
+                ("noise_eps", c_float)]
+
+
+class ArenaGame(ctypes.Structure):
+    _fields_ = [("game_id", c_int), ("board_size", c_int), ("a_is_player1", c_int), ("n_moves", c_int),
+                ("moves", P(MoveRec)), ("mover", P(ctypes.c_uint8)), ("result", c_int), ("score_a", c_float),
+                ("evals_a", c_int64), ("evals_b", c_int64)]
+
+
+class ArenaSummary(ctypes.Structure):
+    _fields_ = [(n, c_int64) for n in ("games", "wins_a", "wins_b", "draws", "moves", "evals_a", "evals_b")] + \
+               [("elo_a", ctypes.c_double), ("elo_b", ctypes.c_double)]
+
+
+ARENA_SINK = ctypes.CFUNCTYPE(None, vp, P(ArenaGame))
 EVAL_FN = ctypes.CFUNCTYPE(c_int, vp, c_int, P(c_int), P(c_int), P(c_int), c_int, P(c_float), c_int, P(c_float),
                            P(c_float))
 GAME_SINK = ctypes.CFUNCTYPE(None, vp, c_int, c_int, c_int, P(MoveRec), c_int)
@@ -89,6 +106,7 @@ EXPORTS = {
     "az_search_seed": (c_int, [vp, c_int, c_uint32]),
     "az_search_get_rng": (c_int, [vp, c_int, vp]),
     "az_search_set_net": (c_int, [vp, vp]),
+    "az_search_set_slot_nets": (c_int, [vp, P(vp), c_int, P(ctypes.c_uint8)]),
     "az_search_run_masked": (c_int, [vp, vp]),
     "az_search_simulate_masked": (c_int, [vp, c_int, vp]),
     "az_search_release_masked": (c_int, [vp, c_int, vp, vp]),
@@ -107,6 +125,14 @@ EXPORTS = {
     "az_selfplay_step": (c_int, [vp, P(SelfPlayCfg), P(c_int64), P(c_int64)]),
     "az_selfplay_step_moves": (c_int, [vp, P(P(MoveRec)), P(P(c_int)), P(c_int)]),
     "az_selfplay_run": (c_int, [vp, P(SelfPlayCfg), c_int, c_int, GAME_SINK, PROGRESS_FN, vp, P(c_int)]),
+    "az_elo_update": (None, [P(ctypes.c_double), P(ctypes.c_double), ctypes.c_double, ctypes.c_double]),
+    "az_arena_create": (c_int, [vp, vp, vp, P(SearchCfg), P(ArenaCfg), P(vp)]),
+    "az_arena_step": (c_int, [vp, P(c_int64)]),
+    "az_arena_run": (c_int, [vp, c_int, c_int, ARENA_SINK, PROGRESS_FN, vp, P(c_int)]),
+    "az_arena_summary_read": (c_int, [vp, P(ArenaSummary)]),
+    "az_arena_table_games": (c_int, [vp, P(c_int)]),
+    "az_arena_search": (vp, [vp]),
+    "az_arena_destroy": (None, [vp]),
     "az_dataset_create": (c_int, [vp, c_int, c_int, P(vp)]),
     "az_dataset_destroy": (None, [vp]),
     "az_dataset_extract": (c_int, [vp, c_int, P(c_int), P(c_int), P(c_int), P(c_float), P(c_int), c_int, P(c_int64),

@@ -7,6 +7,7 @@
 #include <pybind11/pybind11.h>
 #include <pybind11/stl.h>
 
+#include "alphazero/evaluation/arena.h"
 #include "alphazero/nn/torchscript_reader.h"
 #include "alphazero/games/go/go_state.h"
 #include "alphazero/games/gomoku/gomoku_state.h"
@@ -476,6 +477,68 @@ PYBIND11_MODULE(_alphazero_cpp, m) {
         .def_readwrite("noiseSeed", &selfplay::GameShard::noiseSeed);
     m.def("shardGames", &selfplay::shardGames, py::arg("rank"), py::arg("world"), py::arg("totalGames"),
           py::arg("noiseSeed") = 42u);
+
+    // the evaluation match (python/scripts/evaluate.py) and its Elo arithmetic (python/alphazero/utils/elo.py)
+    py::class_<evaluation::EloRating>(m, "EloRating")
+        .def(py::init<double, double>(), py::arg("initialRating") = 1500.0, py::arg("kFactor") = 32.0)
+        .def("getRating", &evaluation::EloRating::getRating)
+        .def("addGameResult", &evaluation::EloRating::addGameResult, py::arg("playerId"), py::arg("opponentId"),
+             py::arg("score"))
+        .def_static("expectedScore", &evaluation::EloRating::expectedScore);
+    py::class_<evaluation::ArenaConfig>(m, "ArenaConfig")
+        .def(py::init<>())
+        .def_readwrite("gameType", &evaluation::ArenaConfig::gameType)
+        .def_readwrite("boardSize", &evaluation::ArenaConfig::boardSize)
+        .def_readwrite("tables", &evaluation::ArenaConfig::tables)
+        .def_readwrite("numSimulations", &evaluation::ArenaConfig::numSimulations)
+        .def_readwrite("cPuct", &evaluation::ArenaConfig::cPuct)
+        .def_readwrite("fpuReduction", &evaluation::ArenaConfig::fpuReduction)
+        .def_readwrite("virtualLoss", &evaluation::ArenaConfig::virtualLoss)
+        .def_readwrite("swapColors", &evaluation::ArenaConfig::swapColors)
+        .def_readwrite("temperature", &evaluation::ArenaConfig::temperature)
+        .def_readwrite("sampleMoves", &evaluation::ArenaConfig::sampleMoves)
+        .def_readwrite("noiseAlpha", &evaluation::ArenaConfig::noiseAlpha)
+        .def_readwrite("noiseEpsilon", &evaluation::ArenaConfig::noiseEpsilon)
+        .def_readwrite("seed", &evaluation::ArenaConfig::seed)
+        .def_readwrite("ttLog2", &evaluation::ArenaConfig::ttLog2);
+    py::class_<evaluation::ArenaGame>(m, "ArenaGame")
+        .def_readonly("gameId", &evaluation::ArenaGame::gameId)
+        .def_readonly("aIsPlayer1", &evaluation::ArenaGame::aIsPlayer1)
+        .def_readonly("moves", &evaluation::ArenaGame::moves)
+        .def_readonly("movers", &evaluation::ArenaGame::movers)
+        .def_readonly("result", &evaluation::ArenaGame::result)
+        .def_readonly("scoreA", &evaluation::ArenaGame::scoreA)
+        .def_readonly("evalsA", &evaluation::ArenaGame::evalsA)
+        .def_readonly("evalsB", &evaluation::ArenaGame::evalsB);
+    py::class_<evaluation::ArenaSummary>(m, "ArenaSummary")
+        .def_readonly("games", &evaluation::ArenaSummary::games)
+        .def_readonly("winsA", &evaluation::ArenaSummary::winsA)
+        .def_readonly("winsB", &evaluation::ArenaSummary::winsB)
+        .def_readonly("draws", &evaluation::ArenaSummary::draws)
+        .def_readonly("moves", &evaluation::ArenaSummary::moves)
+        .def_readonly("evalsA", &evaluation::ArenaSummary::evalsA)
+        .def_readonly("evalsB", &evaluation::ArenaSummary::evalsB)
+        .def_readonly("eloA", &evaluation::ArenaSummary::eloA)
+        .def_readonly("eloB", &evaluation::ArenaSummary::eloB);
+    py::class_<evaluation::Arena>(m, "Arena")
+        .def(py::init<nn::HipNeuralNetwork&, nn::HipNeuralNetwork&, const evaluation::ArenaConfig&>(), py::arg("netA"),
+             py::arg("netB"), py::arg("config"), py::keep_alive<1, 2>(), py::keep_alive<1, 3>())
+        .def("step", [](evaluation::Arena& self) {
+            py::gil_scoped_release release;
+            return self.step();
+        })
+        .def("run", [](evaluation::Arena& self, int totalGames, int maxMoves) {
+            py::gil_scoped_release release;
+            return self.run(totalGames, maxMoves);
+        }, py::arg("totalGames"), py::arg("maxMoves") = 0)
+        .def("summary", &evaluation::Arena::summary)
+        .def("setAbort", &evaluation::Arena::setAbort)
+        .def("setProgressCallback", [](evaluation::Arena& self, std::function<void(int, int, int, int64_t)> cb) {
+            self.setProgressCallback([cb](int g, int mv, int tg, int64_t tm) {
+                py::gil_scoped_acquire acquire;
+                cb(g, mv, tg, tm);
+            });
+        });
 
     py::class_<selfplay::SelfPlayManager>(m, "SelfPlayManager")
         .def(py::init<nn::NeuralNetwork*, int, int, int>(), py::arg("neuralNetwork"), py::arg("numGames") = 100,

@@ -14,6 +14,13 @@ struct az_net;
 struct az_search {
     az_engine* e = nullptr;
     az_net* net = nullptr;
+    // az_search_set_slot_nets: slot g is evaluated by nets[slot_net[g]] (n_nets = 0: the one net above).
+    // Net k's batch is region k of the batch buffers -- rows [k * G, (k + 1) * G) of t.eval_games,
+    // d_logits, d_value and d_batch, counter t.n_eval[k] -- which hold `regions` regions (1 at creation).
+    az_net* nets[AZ_MAX_SLOT_NETS] = {};
+    int n_nets = 0, regions = 1;
+    int net_slots[AZ_MAX_SLOT_NETS] = {};   // slots assigned to each net: its forward's capacity
+    uint8_t* d_slot_net = nullptr;          // [G]
     az_search_cfg c{};
     TreeDev t{};
     Nodes arena[2]{};
@@ -78,6 +85,8 @@ struct az_search {
     std::mutex mu;
 };
 
+// az_search_create; net_batch: the batch capacity `net` must have (az_search_create: n_games).
+int search_create(az_engine* e, az_net* net, const az_search_cfg* c, int net_batch, az_search** out);
 // One search of every playing game: root step, optional noise, the simulations, the error check.
 int search_run(az_search* s);
 // The root noise of the games in mask (null: all): draws on the host, k_noise on the device.

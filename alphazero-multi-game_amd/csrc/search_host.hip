@@ -67,6 +67,13 @@ int check_err(az_search* s) {
     HIPCHK(hipStreamSynchronize(s->e->stream));
     if (err) return az_fail(AZ_ERR_CAPACITY, "device capacity exceeded (flags 0x%x: 1 node pool, 2 path, 4 prior ring)", err);
     if (int r = check_ovf(s->net, ovf)) return r;
+    // per-slot nets: every other net's range guard (nets[0] is s->net, read above)
+    for (int k = 1; k < s->n_nets; ++k) {
+        int o = 0;
+        HIPCHK(hipMemcpyAsync(&o, s->nets[k]->ovf, 4, hipMemcpyDeviceToHost, s->e->stream));
+        HIPCHK(hipStreamSynchronize(s->e->stream));
+        if (int r = check_ovf(s->nets[k], o)) return r;
+    }
     return 0;
 }
 
@@ -121,6 +128,38 @@ int host_evaluate(az_search* s) {
     return 0;
 }
 
+// The network part of a step on a handle with per-slot nets (az_search_set_slot_nets): k_scan_nets
+// partitions the leaves by net, then every net that has slots runs one forward on its own region of
+// the batch buffers (rows [k * G, (k + 1) * G)), its capacity the number of slots assigned to it and its
+// batch size the device counter n_eval[k] -- the host never reads the counts.  The expansion finds a
+// slot's outputs through eval_slot as on a compacted single-net batch.
+int eval_slot_nets(az_search* s, int mode, const TreeDev* dts, hipStream_t st) {
+    const TreeDev& t = s->t;
+    const int G = t.G;
+    const bool go = t.game == GAME_GO;
+    hipLaunchKernelGGL(k_scan_nets, dim3(1), dim3(1024), 0, st, dts, s->d_slot_net, s->n_nets);
+    for (int k = 0; k < s->n_nets; ++k) {
+        const int B = s->net_slots[k];
+        if (B == 0) continue;
+        az_net* n = s->nets[k];
+        const int* games = t.eval_games + (size_t)k * G;
+        const int* nb = t.n_eval + k;
+        float* logits = s->d_logits + (size_t)k * G * t.NA;
+        float* value = s->d_value + (size_t)k * G;
+        const bool in_place = net_input_path(n) != NET_IN_GEMM;
+        const LeafRecs lr{t.leafrec, games, go, G, 0};
+        float* x = s->d_batch + (size_t)k * G * t.A * 16;
+        if (!in_place) az_launch_rec_planes(t.leafrec, x, games, nb, lr.go, t.bs, B, st);
+        const bool prof = n->prof;
+        if (mode != MODE_SIM) n->prof = false;   // time only the simulation batches
+        const int r = in_place ? net_forward(n, nullptr, B, nb, logits, value, st, &lr)
+                               : net_forward(n, x, B, nb, logits, value, st);
+        n->prof = prof;
+        if (r) return r;
+    }
+    return 0;
+}
+
 // pre: this step's selection was already issued (fused into the previous step's expansion);
 // fuse_next: issue this step's expansion fused with the next simulation step's selection.
 int search_step(az_search* s, int mode, bool pre = false, bool fuse_next = false) {
@@ -141,6 +180,9 @@ int search_step(az_search* s, int mode, bool pre = false, bool fuse_next = false
         if (int r = host_evaluate(s)) return r;
     }
     TreeDev tt = s->t;
+    if (s->c.eval_kind == AZ_EVAL_NET && s->n_nets > 0) {
+        if (int r = eval_slot_nets(s, mode, dts, st)) return r;
+    } else
     if (s->c.eval_kind == AZ_EVAL_NET) {
         // The batch: in a simulation step with every game active, every game has a leaf and nearly
         // all of them need the network (C3: 800 evaluations per 800-sim move), so the batch is the
@@ -496,6 +538,14 @@ int az_diag_set_tree_stamps(int game) {
 int az_diag_set_sync_every(int n) { g_sync_every = n; return 0; }
 
 int az_search_create(az_engine* e, az_net* net, const az_search_cfg* c, az_search** out) {
+    return search_create(e, net, c, c ? c->n_games : 0, out);
+}
+
+}  // extern "C"
+
+// az_search_create with the batch capacity asked of `net` given apart from the number of games: the
+// arena's handle (arena.hip) gives each of its two nets half of its slots at once.
+int search_create(az_engine* e, az_net* net, const az_search_cfg* c, int net_batch, az_search** out) {
     if (!e || !c || !out) return az_fail(AZ_ERR_ARG, "null argument");
     const int bs = c->board_size, A = bs * bs, G = c->n_games;
     const bool go = c->game == AZ_GAME_GO;
@@ -509,7 +559,7 @@ int az_search_create(az_engine* e, az_net* net, const az_search_cfg* c, az_searc
         if (!net) return az_fail(AZ_ERR_ARG, "AZ_EVAL_NET needs a network");
         if (net->d.board_size != bs || net->d.action_size != NA || net->d.in_planes != (go ? 8 : 11))
             return az_fail(AZ_ERR_ARG, "network shape does not match the board");
-        if (net->d.max_batch < G) return az_fail(AZ_ERR_ARG, "network max_batch %d < n_games %d", net->d.max_batch, G);
+        if (net->d.max_batch < net_batch) return az_fail(AZ_ERR_ARG, "network max_batch %d < n_games %d", net->d.max_batch, net_batch);
         if (!net->loaded) return az_fail(AZ_ERR_STATE, "network weights not loaded");
     }
     if (c->prior_ring > 0 && c->prior_ring < NA)
@@ -620,6 +670,8 @@ int az_search_create(az_engine* e, az_net* net, const az_search_cfg* c, az_searc
     return 0;
 }
 
+extern "C" {
+
 void az_search_destroy(az_search* s) {
     if (s) { pf_wait(s); s->pc.release(); s->pcf.release(); }
     if (!s) return;
@@ -645,7 +697,7 @@ void az_search_destroy(az_search* s) {
                           (const void*)s->d_values, (const void*)s->d_probs, (const void*)s->d_cact, (const void*)s->d_nch,
                           (const void*)s->d_term, (const void*)s->d_res, (const void*)s->d_rexp, (const void*)s->d_games, (const void*)s->d_seed_ids, (const void*)s->d_temps,
                           (const void*)s->d_rc, (const void*)s->d_rcf, (const void*)s->d_thr, (const void*)s->d_pruned,
-                          (const void*)s->d_tree})
+                          (const void*)s->d_tree, (const void*)s->d_slot_net})
         F(p);
     if (s->h_tree) (void)hipHostFree(s->h_tree);
     delete s;
@@ -847,6 +899,77 @@ int az_search_set_net(az_search* s, az_net* net) {
     if (!net->loaded) return az_fail(AZ_ERR_STATE, "network weights not loaded");
     std::lock_guard<std::mutex> lk(s->mu);
     s->net = net;
+    s->n_nets = 0;   // back to one net for every slot (the region buffers stay: region 0 is the batch)
+    return 0;
+}
+
+// Per-slot nets: slot g is evaluated by nets[slot_net[g]] from the next step on; trees, transposition
+// tables and generators kept.  Every argument is checked before the handle changes.
+int az_search_set_slot_nets(az_search* s, az_net* const* nets, int n_nets, const uint8_t* slot_net) {
+    if (!s || !nets || !slot_net) return az_fail(AZ_ERR_ARG, "null argument");
+    if (s->c.eval_kind != AZ_EVAL_NET) return az_fail(AZ_ERR_STATE, "the handle was not created with AZ_EVAL_NET");
+    if (n_nets < 1 || n_nets > AZ_MAX_SLOT_NETS) return az_fail(AZ_ERR_ARG, "n_nets %d outside 1..%d", n_nets, AZ_MAX_SLOT_NETS);
+    static_assert(AZ_MAX_SLOT_NETS == AZ_SCAN_NETS, "k_scan_nets partitions by AZ_MAX_SLOT_NETS nets");
+    const int G = s->c.n_games, bs = s->c.board_size, A = s->t.A, NA = s->t.NA;
+    const bool go = s->c.game == AZ_GAME_GO;
+    int count[AZ_MAX_SLOT_NETS] = {};
+    for (int g = 0; g < G; ++g) {
+        if (slot_net[g] >= n_nets) return az_fail(AZ_ERR_ARG, "slot %d: net index %d >= n_nets %d", g, slot_net[g], n_nets);
+        ++count[slot_net[g]];
+    }
+    for (int k = 0; k < n_nets; ++k) {
+        const az_net* net = nets[k];
+        if (!net) return az_fail(AZ_ERR_ARG, "net %d is null", k);
+        if (net->e != s->e) return az_fail(AZ_ERR_ARG, "net %d lives on another engine", k);
+        if (net->d.board_size != bs || net->d.action_size != NA || net->d.in_planes != (go ? 8 : 11))
+            return az_fail(AZ_ERR_ARG, "net %d: shape does not match the board", k);
+        if (net->d.max_batch < count[k])
+            return az_fail(AZ_ERR_ARG, "net %d: max_batch %d < its %d slots", k, net->d.max_batch, count[k]);
+        if (!net->loaded) return az_fail(AZ_ERR_STATE, "net %d: weights not loaded", k);
+    }
+    std::lock_guard<std::mutex> lk(s->mu);
+    HIPCHK(hipSetDevice(s->e->device));
+    hipStream_t st = s->e->stream;
+    int* games = nullptr; int* n_eval = nullptr; float* logits = nullptr; float* value = nullptr; float* batch = nullptr;
+    uint8_t* sn = nullptr;
+    const bool grow = n_nets > s->regions;
+    int r = 0;
+    if (grow) {
+        const size_t R = (size_t)n_nets;
+        if (!r) r = dalloc(&games, R * G);
+        if (!r) r = dalloc(&n_eval, R);
+        if (!r) r = dalloc(&logits, R * G * NA);
+        if (!r) r = dalloc(&value, R * G);
+        if (!r) r = dalloc(&batch, R * G * A * 16);
+    }
+    if (!r) r = dalloc(&sn, (size_t)G);   // a fresh assignment buffer: a failed upload leaves the old one whole
+    hipError_t he = hipStreamSynchronize(st);   // no queued kernel reads the old buffers or the old assignment
+    if (!r && he != hipSuccess) r = az_fail(AZ_ERR_HIP, "az_search_set_slot_nets: %s", hipGetErrorString(he));
+    if (!r && grow && (hipMemset(games, 0, (size_t)n_nets * G * 4) != hipSuccess || hipMemset(n_eval, 0, (size_t)n_nets * 4) != hipSuccess))
+        r = az_fail(AZ_ERR_HIP, "az_search_set_slot_nets: memset");
+    if (!r && hipMemcpy(sn, slot_net, (size_t)G, hipMemcpyHostToDevice) != hipSuccess)
+        r = az_fail(AZ_ERR_HIP, "az_search_set_slot_nets: slot_net upload");
+    if (r) {   // the handle as it was
+        for (void* p : {(void*)games, (void*)n_eval, (void*)logits, (void*)value, (void*)batch, (void*)sn})
+            if (p) (void)hipFree(p);
+        return r;
+    }
+    if (grow) {
+        for (void* p : {(void*)s->t.eval_games, (void*)s->t.n_eval, (void*)s->d_logits, (void*)s->d_value, (void*)s->d_batch})
+            if (p) (void)hipFree(p);
+        s->t.eval_games = games; s->t.n_eval = n_eval;
+        s->d_logits = logits; s->d_value = value; s->d_batch = batch;
+        s->t.net_logits = logits; s->t.net_value = value;
+        s->regions = n_nets;
+    }
+    if (s->d_slot_net) (void)hipFree(s->d_slot_net);
+    s->d_slot_net = sn;
+    for (int k = 0; k < AZ_MAX_SLOT_NETS; ++k) {
+        s->nets[k] = k < n_nets ? nets[k] : nullptr;
+        s->net_slots[k] = k < n_nets ? count[k] : 0;
+    }
+    s->n_nets = n_nets;
+    s->net = nets[0];
     return 0;
 }
 

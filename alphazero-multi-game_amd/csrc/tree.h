@@ -10,7 +10,8 @@
 
 #define AZ_MAXA 361          // largest board handled on device (19x19)
 #define AZ_MAXNA 362         // largest action space (Go 19x19: 361 points + pass)
-#define AZ_DMAX 96           // longest selection path (root + 95 plies); overflow => AZ_ERR_CAPACITY
+#define AZ_SCAN_NETS 4        // nets k_scan_nets partitions a leaf batch by (AZ_MAX_SLOT_NETS of az_engine.h)
+#define AZ_DMAX 96          // longest selection path (root + 95 plies); overflow => AZ_ERR_CAPACITY
 #define AZ_NCNT 8            // per-game counters
 // Go leaf state (k_select -> k_expand_backup): [0, 384) board, [384, 416) int32 {player, ko, passes,
 // nph} + u64 stones hash, [416, 416 + 8 * AZ_DMAX) u64 position pushes of the path

@@ -992,6 +992,57 @@ __global__ __launch_bounds__(1024) void k_scan(const TreeDev* __restrict__ tp) {
     if (tid == 1023) *t.n_eval = part[1023];
 }
 
+// K2 of a handle whose slots are evaluated by different nets (az_search_set_slot_nets): the stable
+// partition of the leaves that need a network by slot_net[g], one block.  Net k owns region k -- rows
+// [k * G, (k + 1) * G) of eval_games (and of the logits / values its forward writes): a slot's row is
+// k * G + its rank among net k's leaves in slot order, n_eval[k] counts them.  The four nets' scans run
+// together (one int4 per thread); a net without a leaf gets n_eval[k] = 0.
+__global__ __launch_bounds__(1024) void k_scan_nets(const TreeDev* __restrict__ tp, const uint8_t* __restrict__ slot_net,
+                                                    int n_nets) {
+    const TreeDev& t = *tp;
+    __shared__ int4 part[1024];
+    const int tid = threadIdx.x;
+    const int G = t.G;
+    const int per = (G + 1023) / 1024;
+    const int b0 = tid * per;
+    int s[AZ_SCAN_NETS] = {0, 0, 0, 0};
+    for (int i = 0; i < per; ++i) {
+        const int g = b0 + i;
+        if (g < G && t.need_eval[g]) {
+            const int k = min((int)slot_net[g], n_nets - 1);
+#pragma unroll
+            for (int j = 0; j < AZ_SCAN_NETS; ++j) s[j] += k == j;
+        }
+    }
+    part[tid] = int4{s[0], s[1], s[2], s[3]};
+    __syncthreads();
+    for (int o = 1; o < 1024; o <<= 1) {
+        const int4 v = tid >= o ? part[tid - o] : int4{0, 0, 0, 0};
+        __syncthreads();
+        int4 p = part[tid];
+        p.x += v.x; p.y += v.y; p.z += v.z; p.w += v.w;
+        part[tid] = p;
+        __syncthreads();
+    }
+    const int4 incl = part[tid];
+    int off[AZ_SCAN_NETS] = {incl.x - s[0], G + incl.y - s[1], 2 * G + incl.z - s[2], 3 * G + incl.w - s[3]};
+    for (int i = 0; i < per; ++i) {
+        const int g = b0 + i;
+        if (g >= G) break;
+        if (!t.need_eval[g]) { t.eval_slot[g] = -1; continue; }
+        const int k = min((int)slot_net[g], n_nets - 1);
+        int row = 0;
+#pragma unroll
+        for (int j = 0; j < AZ_SCAN_NETS; ++j)
+            if (k == j) { row = off[j]; ++off[j]; }
+        t.eval_slot[g] = row; t.eval_games[row] = g;
+    }
+    if (tid == 1023) {
+        const int tot[AZ_SCAN_NETS] = {incl.x, incl.y, incl.z, incl.w};
+        for (int k = 0; k < n_nets; ++k) t.n_eval[k] = tot[k];
+    }
+}
+
 // K3: evaluator output -> TT store -> expansion -> backup.
 // Latency layout: every per-game input (status, path, cached leaf value / hash / batch slot, root
 // board, TT / ring / pool cursors, counters) is loaded before anything waits -- one round trip --

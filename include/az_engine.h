@@ -255,6 +255,17 @@ int az_search_set_params(az_search* s, const az_search_cfg* cfg);
  * setNeuralNetwork, parallel_mcts.cpp:1190-1207, only replaces nn_): same engine, board, planes
  * and action space, max_batch >= n_games, weights loaded; else AZ_ERR_ARG / AZ_ERR_STATE. */
 int az_search_set_net(az_search* s, az_net* net);
+/* Per-slot nets on an AZ_EVAL_NET handle: slot g is evaluated by nets[slot_net[g]] (slot_net holds
+ * n_games entries), so one lock-step search plays the slots of two ParallelMCTS objects that hold
+ * different models (python/scripts/evaluate.py:186-291 builds one per model).  Every simulation step
+ * partitions its leaf batch by net on the device and runs one forward per net that has slots.  Each
+ * net must satisfy what az_search_set_net demands, with max_batch >= the number of slots assigned
+ * to it.  n_nets outside 1..AZ_MAX_SLOT_NETS, an index >= n_nets, a mismatched net (AZ_ERR_ARG), an
+ * unloaded net or a handle that is not AZ_EVAL_NET (AZ_ERR_STATE) leave the handle as it was.
+ * Trees, transposition tables and generators are kept; a slot plays bit for bit what it plays on
+ * a single-net handle with its own net.  A later az_search_set_net returns to one net. */
+#define AZ_MAX_SLOT_NETS 4
+int az_search_set_slot_nets(az_search* s, az_net* const* nets, int n_nets, const uint8_t* slot_net);
 /* Empty every game's transposition table, trees kept (ParallelMCTS::setTranspositionTable with a
  * new table, parallel_mcts.cpp:1209-1222). */
 int az_search_clear_tt(az_search* s);
@@ -340,6 +351,71 @@ typedef void (*az_progress_fn)(void* user, int game_id, int move_num, int total_
  * polled between moves (setAbort).  Returns 0 or an error code. */
 int az_selfplay_run(az_search* s, const az_selfplay_cfg* cfg, int total_games, int max_moves, az_game_sink sink,
                     az_progress_fn progress, void* user, const volatile int* abort_flag);
+
+/* ----------------------------------------------------------------- arena */
+/* The evaluation match of python/scripts/evaluate.py (play_game :186-291, run_evaluation :294-460):
+ * net A against net B on `search->n_games` tables in lock step.  The arena owns one az_search with
+ * two slots per table -- slot 2i is A's tree of table i, slot 2i + 1 is B's (evaluate.py builds one
+ * ParallelMCTS per model and game, :376-384) -- and per-slot nets 0,1,0,1,... (az_search_set_slot_nets).
+ * Per ply the side to move searches its own tree and picks selectAction(true, T) (:199-220); the move is
+ * applied to both trees of the table (:243-247).  The two trees of game id `gid` are started with the
+ * stream ids 2 gid and 2 gid + 1 (az_search_new_games_ids), so a game's record does not depend on the
+ * number of tables.  Deviations: every tree has a transposition table of its own, emptied when its
+ * game starts (evaluate.py shares one table per model across games, :336-337); no time control and
+ * no variant rules. */
+typedef struct az_arena az_arena;
+typedef struct az_arena_cfg {
+    int swap_colors;      /* evaluate.py --swap (:365-370): odd game ids give player 1 to B */
+    float temperature;    /* selectAction(true, T), :220; evaluate.py's default is 0.1 */
+    int sample_moves;     /* the first sample_moves plies of a game are drawn with the stochastic
+                             selectAction branch (az_search_select_action, batch_inference = 0);
+                             0: the deterministic rule of az_search_select on every ply */
+    float noise_alpha, noise_eps;   /* addDirichletNoise on the mover's root before its search;
+                                       noise_eps 0: none (evaluate.py adds none) */
+} az_arena_cfg;
+/* One finished game.  moves[i] was played by net mover[i] (0: A, 1: B) with the root value and the
+ * child-order visit distribution of the mover's tree.  result: core::GameResult, ONGOING for a game
+ * cut at max_moves.  score_a: 1 / 0.5 / 0 by the colour A played (evaluate.py:259-278; a cut game
+ * scores 0.5).  evals_a / evals_b: network evaluations of the game's two trees. */
+typedef struct az_arena_game {
+    int game_id;
+    int board_size;
+    int a_is_player1;
+    int n_moves;
+    const az_move_rec* moves;
+    const uint8_t* mover;
+    int result;
+    float score_a;
+    int64_t evals_a, evals_b;
+} az_arena_game;
+typedef struct az_arena_summary {
+    int64_t games, wins_a, wins_b, draws, moves, evals_a, evals_b;
+    double elo_a, elo_b;   /* EloRating(1500, 32) over the finished games in game-id order */
+} az_arena_summary;
+/* Receives every finished game once, on the calling thread between plies; valid during the call. */
+typedef void (*az_arena_sink)(void* user, const az_arena_game* game);
+/* One EloRating.add_game_result (python/alphazero/utils/elo.py:12-40, :70-101) in doubles: both ratings
+ * move by k (score - expected), each expectation taken from the ratings before the game. */
+void az_elo_update(double* rating_a, double* rating_b, double score_a, double k_factor);
+/* search: the per-tree configuration (AZ_EVAL_NET; n_games = tables; tt_log2 20 is the reference's
+ * table size, evaluate.py:336-337).  Both nets need max_batch >= tables. */
+int az_arena_create(az_engine* e, az_net* a, az_net* b, const az_search_cfg* search, const az_arena_cfg* cfg,
+                    az_arena** out);
+/* One ply on every live table.  Outside az_arena_run the tables play game ids 0, 1, ... without end
+ * (a finished table takes the next id, in table order). */
+int az_arena_step(az_arena* a, int64_t* moves_done);
+/* total_games games, ids 0..total_games-1, from fresh tables: a table whose game ends -- or is cut
+ * at max_moves (> 0) -- takes the next id in table order while ids remain, then sits idle.  progress
+ * is called for every move after it is chosen and before it is applied (the handle of
+ * az_arena_search may be read from it); abort_flag is polled between plies. */
+int az_arena_run(az_arena* a, int total_games, int max_moves, az_arena_sink sink, az_progress_fn progress,
+                 void* user, const volatile int* abort_flag);
+int az_arena_summary_read(az_arena* a, az_arena_summary* out);
+/* The game id each table plays now (-1: idle); game_ids holds `tables` entries. */
+int az_arena_table_games(az_arena* a, int* game_ids);
+/* The underlying handle (tests, the evaluation log, counters); owned by the arena. */
+az_search* az_arena_search(az_arena* a);
+void az_arena_destroy(az_arena* a);
 
 /* --------------------------------------------------------------- dataset */
 /* alphazero::selfplay::Dataset (include/alphazero/selfplay/dataset.h:33-118,
