@@ -182,6 +182,12 @@ class HipNeuralNetwork:
         check(lib().az_net_trunk_kernel(self.h, buf, 128))
         return buf.value.decode()
 
+    def plan(self):
+        """Diagnostic: how this net runs at its current precision (input stage, trunk family, tail, head FCs)."""
+        buf = ctypes.create_string_buffer(256)
+        check(lib().az_diag_net_plan(self.h, buf, 256))
+        return buf.value.decode()
+
     def getBatchSize(self):
         return self.desc.max_batch
 

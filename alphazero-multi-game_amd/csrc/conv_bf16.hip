@@ -1765,12 +1765,8 @@ __global__ __launch_bounds__(256) void k_pool_heads_g8(const uint16_t* hi, const
     }
 }
 
-// true when k_pool_heads_g8 takes this tail: 32-channel slices, at most 64 cells, both heads' 1x1
-// convs = 64 outputs, the joined slice within the LDS budget
-// k_pool_heads_g8's dynamic LDS: the board's pooled-cell partial sums + two 64 x 33 weight tiles
-static size_t pool_heads_lds(int H) { return ((size_t)H * H * 36 + 2 * 64 * 33) * sizeof(float); }
-// the device's LDS per workgroup (68.9 KB at 19x19 fits gfx950's 160 KB, not a 64 KB part)
-static size_t device_lds_limit() {
+// the device's LDS per workgroup (k_pool_heads_g8's dynamic LDS, az_pool_heads_lds, must fit)
+size_t az_device_lds_limit() {
     static const size_t lim = [] {
         int dev = 0, v = 0;
         if (hipGetDevice(&dev) != hipSuccess ||
@@ -1780,27 +1776,15 @@ static size_t device_lds_limit() {
     }();
     return lim;
 }
-bool az_pool_heads_supported(int C, int H, int P, int N) {
-    return C % 32 == 0 && P * P <= 64 && N == 64 && H * H <= 361 && pool_heads_lds(H) <= device_lds_limit();
-}
-
 int az_launch_pool_heads_g8(const uint16_t* hi, const int8_t* q, const float* Wt, const float* bias, float* out, int B,
                             int C, int H, int P, int N, const int* m_limit, int mode, hipStream_t st) {
-    if (!az_pool_heads_supported(C, H, P, N)) return -1;
-    const size_t lds = pool_heads_lds(H);
+    if (!az_pool_heads_supported(C, H, P, N, az_device_lds_limit())) return -1;
+    const size_t lds = az_pool_heads_lds(H);
     if (mode == 2) hipLaunchKernelGGL(k_pool_heads_g8<2>, dim3(B), dim3(256), lds, st, hi, q, Wt, bias, out, C, H, P, m_limit, B);
     else if (mode == 0) hipLaunchKernelGGL(k_pool_heads_g8<0>, dim3(B), dim3(256), lds, st, hi, q, Wt, bias, out, C, H, P, m_limit, B);
     else if (mode == 3) hipLaunchKernelGGL(k_pool_heads_g8<3>, dim3(B), dim3(256), lds, st, hi, q, Wt, bias, out, C, H, P, m_limit, B);
     else hipLaunchKernelGGL(k_pool_heads_g8<1>, dim3(B), dim3(256), lds, st, hi, q, Wt, bias, out, C, H, P, m_limit, B);
     return hipGetLastError() == hipSuccess ? 0 : -2;
-}
-
-// true when the g8 trunk (conv3x3_v5 at 15x15 / conv3x3_v6) handles this shape: square boards with a
-// G8Geom instantiation, 128-channel output halves, 16-channel chunks (v5, 15x15) or 32 (v6)
-static bool g8_board(int H) { return H == 8 || H == 9 || H == 13 || H == 15 || H == 19; }
-bool az_conv_g8_supported(int H, int W, int C, int N) {
-    if (H != W || !g8_board(H) || N % 128 != 0 || C < 16) return false;
-    return H == 15 ? C % 16 == 0 : C % 32 == 0;
 }
 
 static int g_conv_flags = 4 | 0x200;   // bit 2: v6 (16x16x32) at 15x15; 0x200: v7 on 15x15 boards only
@@ -1857,12 +1841,10 @@ static int g8_choice(const ConvBf16Args& a, int* geo) {
         *geo = 2;
         return 1;
     }
-    const size_t HW = (size_t)a.H * a.W;
     if (a.a_tail < (size_t)a.M * a.C * 2) return 0;
     // v6: the padding offset walks (C/32) chunk steps of 4*HW*16 B into the zeroed tail, and the
     // buffer descriptor's 32-bit range must cover the activations plus that tail
-    const bool v6_ok = a.C % 32 == 0 && a.a_tail + AZ_ACT_TAIL * 2 < ((size_t)1 << 31) &&
-                       (size_t)(a.C / 32) * 4 * HW * 16 + 16 <= AZ_ACT_TAIL * 2;
+    const bool v6_ok = a.C % 32 == 0 && az_act_range_ok(a.a_tail) && az_tail_reach_ok(a.H, a.C);
     if (a.H != 15 || ((a.flags & 4) && a.C % 32 == 0)) {
         if (!v6_ok || !a.relu) return 0;                 // conv3x3_v6 always applies the ReLU
         *geo = (a.flags & 8) || (a.H != 15 && !(a.flags & 0x4000000));
@@ -1937,9 +1919,6 @@ void az_launch_to_f16(const float* in, uint16_t* out, size_t n, const int* m_lim
                       hipStream_t st, int* ovf) {
     hipLaunchKernelGGL(k_to_f16, dim3(2048), dim3(256), 0, st, in, out, n, m_limit, rows_per_sample, C, ovf);
 }
-
-// true when conv3x3_v4 handles this shape
-bool az_conv_v4_supported(int H, int W, int C, int N) { return H == 15 && W == 15 && C % 16 == 0 && N % 64 == 0; }
 
 template <int BNT>
 static void v4_launch(const ConvBf16Args& a, int mode, int grid, hipStream_t st) {

@@ -1307,26 +1307,17 @@ int az_conv_v7_ring(const ConvBf16Args& a) {
 
 // true when conv3x3_v7 takes this layer
 bool az_conv_v7_supported(const ConvBf16Args& a) {
-    if (a.H != a.W || a.C % 64 || a.N % 128 || !a.relu || a.Cf || a.Clo) return false;
-    const int HB = a.H;
-    if (HB != 8 && HB != 9 && HB != 13 && HB != 15 && HB != 19) return false;
-    const size_t HW = (size_t)HB * HB;
-    // the padding offset walks C/32 chunk steps into the zeroed tail; 32-bit buffer ranges
-    return a.a_tail + AZ_ACT_TAIL * 2 < ((size_t)1 << 31) && (size_t)(a.C / 32) * 4 * HW * 16 + 16 <= AZ_ACT_TAIL * 2 &&
-           (size_t)9 * a.C * a.N * 2 < ((size_t)1 << 31);
+    if (!a.relu || a.Cf || a.Clo) return false;
+    return az_conv_v7_shape_supported(a.H, a.W, a.C, a.N, a.a_tail);
 }
 
 // conv3x3_v7x3 (AZ_PREC_BF16X3 on the g8 hi / lo planes): same shapes as conv3x3_v7, plus the lo
 // planes of the input and the weights and both output planes; a residual needs both of its planes
 bool az_conv_v7x3_supported(const ConvBf16Args& a) {
-    if (a.H != a.W || a.C % 64 || a.N % 128 || !a.relu || a.Cf || a.Cq || a.Rq) return false;
+    if (!a.relu || a.Cf || a.Cq || a.Rq) return false;
     if (!a.Ahi || !a.Alo || !a.Bblk || !a.Bblk_lo || !a.Chi || !a.Clo || (!a.Rhi) != (!a.Rlo)) return false;
     if (a.pt == 2 && !a.oscale) return false;             // fp16 pieces: the weights' per-channel scale
-    const int HB = a.H;
-    if (HB != 8 && HB != 9 && HB != 13 && HB != 15 && HB != 19) return false;
-    const size_t HW = (size_t)HB * HB;
-    return a.a_tail >= (size_t)a.M * a.C * 2 && a.a_tail + AZ_ACT_TAIL * 2 < ((size_t)1 << 31) &&
-           (size_t)(a.C / 32) * 4 * HW * 16 + 16 <= AZ_ACT_TAIL * 2 && (size_t)9 * a.C * a.N * 2 < ((size_t)1 << 31);
+    return a.a_tail >= (size_t)a.M * a.C * 2 && az_conv_v7_shape_supported(a.H, a.W, a.C, a.N, a.a_tail);
 }
 
 template <int HB, int GEO>
@@ -1372,7 +1363,7 @@ static bool x3_wide(const ConvBf16Args& a) { return a.N % 256 == 0 && !(az_conv_
 
 // the kernel az_conv_v7x3_launch takes (bench.py's roofline label)
 int az_conv_x3_name(const ConvBf16Args& a, char* out, int len) {
-    if (!az_conv_v7x3_supported(a)) return -1;
+    if (!az_conv_v7_shape_supported(a.H, a.W, a.C, a.N, a.a_tail)) return -1;
     snprintf(out, len, "%s<%d, %s%s>", x3_wide(a) ? "conv3x3_v9x3" : "conv3x3_v7x3", a.H, a.H == 15 ? "SLIM" : "DENSE",
              a.pt == 2 ? ", f16" : "");
     return 0;

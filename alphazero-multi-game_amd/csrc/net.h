@@ -1,9 +1,11 @@
 // net.h -- launch interface of the ConvNet kernels (net_kernels.hip, conv_bf16.hip, conv_v7.hip,
 // smallnet.hip): the one declaration of every launcher, included by the file that defines it and
-// by every file that calls it.
+// by every file that calls it.  The shape predicates the launchers guard with are in net_plan.h.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
+
+#include "net_plan.h"
 
 enum { ACT_NONE = 0, ACT_RELU = 1, ACT_TANH = 2 };
 
@@ -32,9 +34,6 @@ struct GemmArgs {
 };
 
 // bf16 trunk conv: activations stored as bf16 hi (+ lo) planes, NHWC.
-// zeroed tail after every 16-bit activation buffer (elements): the v6 conv's padding source
-constexpr size_t AZ_ACT_TAIL = 262144;   // zeroed 16-bit elements behind every g8 activation buffer (512 KB)
-
 struct ConvBf16Args {
     const uint16_t* Ahi; const uint16_t* Alo;   // [rows][C] bf16 (Alo null for plain bf16)
     const uint16_t* Bhi; const uint16_t* Blo;   // [N][9*C] bf16
@@ -81,8 +80,6 @@ struct SmallNetArgs {
     int pt;                         // k_smallnet_x3 pieces: 1 bf16, 2 fp16 (weights scaled by 2^s per output channel,
     const float* osc;               // bias = b * 2^s; osc [L][64] = 2^-s)
 };
-bool az_smallnet_supported(int H, int C, int cin_pad, int pool, int head_channels);
-int az_smallnet_max_blocks();
 int az_smallnet_launch(const SmallNetArgs& a, int B, hipStream_t st);
 int az_smallnet_stamps_mode();        // az_diag_set_smallnet_stamps (0: off)
 
@@ -128,9 +125,7 @@ void az_launch_rec_planes(const uint8_t* rec, float* dst, const int* eval_games,
 int az_conv_flags();                  // kernel variant bits (az_diag_set_conv_flags)
 void az_conv_bf16_launch_v(const ConvBf16Args& a, bool split, hipStream_t st);
 int az_conv_bf16_name(const ConvBf16Args& a, int mode, char* out, int len);
-bool az_conv_v4_supported(int H, int W, int C, int N);
 void az_conv_v4_launch(const ConvBf16Args& a, int mode, hipStream_t st);
-bool az_conv_g8_supported(int H, int W, int C, int N);
 int az_conv_g8_launch(const ConvBf16Args& a, int mode, hipStream_t st);
 int az_conv_g8_name(const ConvBf16Args& a, int mode, char* out, int len);
 void az_launch_to_g8(const float* in, uint16_t* hi, int8_t* q, int C, int HW, const int* m_limit, int maxB, int mode,
@@ -145,7 +140,7 @@ void az_launch_split_bf16(const float* in, uint16_t* hi, uint16_t* lo, size_t n,
                           int C, hipStream_t st);
 void az_launch_pool_g8(const uint16_t* hi, const int8_t* q, float* out, int B, int C, int H, int P, const int* m_limit,
                        int mode, hipStream_t st);
-bool az_pool_heads_supported(int C, int H, int P, int N);
+size_t az_device_lds_limit();         // LDS per workgroup of the current device (az_pool_heads_supported's limit)
 int az_launch_pool_heads_g8(const uint16_t* hi, const int8_t* q, const float* Wt, const float* bias, float* out, int B,
                             int C, int H, int P, int N, const int* m_limit, int mode, hipStream_t st);
 

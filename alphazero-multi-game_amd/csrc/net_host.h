@@ -41,7 +41,7 @@ struct RwBlock {
 struct az_net {
     az_engine* e = nullptr;
     az_net_desc d{};
-    int cin_pad = 16;
+    int cin_pad = 16;         // NetShape::cin_pad (net_plan.h)
     int HW = 0, P2 = 0;
     size_t act_elems = 0;   // elements of every 16-bit activation buffer before its zeroed tail
     size_t nparams = 0;
@@ -101,11 +101,7 @@ struct az_net {
 // The parameters of the net's canonical blob (net_load.hip: the plain or the rand-wire layout).
 size_t net_blob_params(const az_net* n);
 
-// How the forward reads its input planes: NET_IN_SMALL (k_smallnet), NET_IN_G8 (k_to_g8 + the
-// g8 input conv) -- both can build board b's planes from the search's leaf record gidx[b]
-// (leaf_planes.h), so the search hands its leaves over without a plane batch -- or NET_IN_GEMM
-// (f32 input conv on x0).
-enum { NET_IN_GEMM = 0, NET_IN_SMALL = 1, NET_IN_G8 = 2 };
+// How the forward reads its input planes: the plan's NET_IN_* (net_plan.h).
 int net_input_path(const az_net* n);
 
 struct LeafRecs {                 // the search's leaf records: sample b = record gidx[b] (n records)

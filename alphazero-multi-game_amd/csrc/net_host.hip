@@ -1,6 +1,6 @@
 // net_host.hip -- the device network behind the az_net_* entry points of include/az_engine.h:
-// creation (buffers, shape and precision checks), the forward with its kernel dispatch, profiling.
-// The weights are loaded by net_load.hip.
+// creation (buffers, shape and precision checks), the forward dispatched on the net's plan
+// (net_plan.h), profiling.  The weights are loaded by net_load.hip.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -17,6 +17,10 @@
 
 namespace {
 
+NetPlan plan_of(const az_net* n) {
+    return net_plan(net_shape(n->d, n->rw), n->d.precision, az_conv_flags(), az_device_lds_limit());
+}
+
 GemmArgs gemm_args(const Layer& L, const float* A, int lda, float* C, int ldc, const float* res, int M, int H, int W,
                    const int* m_limit, int rows_per_sample) {
     GemmArgs p{};
@@ -26,87 +30,52 @@ GemmArgs gemm_args(const Layer& L, const float* A, int lda, float* C, int ldc, c
     return p;
 }
 
-// K slices for an FC layer of B rows: enough blocks to cover the chip (a 128 x 128 f32 tile is
-// bound by the CU's f32 MFMA rate), slices of >= 64 K
-constexpr int FC_MAX_SPLITS = 64;
-static int fc_splits(int B, int K) {
-    const int tiles = (B + 127) / 128 * 2;
-    int s = 1;
-    while (s < FC_MAX_SPLITS && tiles * s < 512 && K / (2 * s) >= 64) s *= 2;
-    return s;
-}
-
-int net_heads_fc(az_net* n, int B, const int* nb, float* logits, float* value, hipStream_t st,
-                 const float* pp = nullptr, const float* vp = nullptr, int xs = 0);
-
-// Trunk conv i (0: first conv of a block, 1: second) of an AZ_PREC_BF16X3 / AZ_PREC_F16X3 net on the
-// g8 hi / lo planes (conv3x3_v9x3 / v7x3): input / output / residual plane pairs by ping-pong index `cur`.
-ConvBf16Args x3_conv_args(const az_net* n, const Layer& L, int second, int cur, int B, const int* nb) {
-    const az_net_desc& d = n->d;
+// What every 3x3 conv of a forward of B boards shares (C input channels, the net's channels out, ReLU,
+// the zeroed tail behind the full capacity); the caller states operands, outputs and residuals.
+ConvBf16Args conv_args(const az_net* n, int B, const int* nb, int C) {
     ConvBf16Args a{};
-    a.Ahi = second ? n->th : n->hh[cur]; a.Alo = second ? n->tl : n->hl[cur];
-    a.Bblk = L.Wbk_bf; a.Bblk_lo = L.Wbk_lo;
-    a.pt = d.precision == AZ_PREC_F16X3 ? 2 : 1;
-    if (a.pt == 2) { a.Bblk = L.Wbk_fh; a.Bblk_lo = L.Wbk_fl; a.oscale = L.sx; }
-    a.Chi = second ? n->hh[cur ^ 1] : n->th; a.Clo = second ? n->hl[cur ^ 1] : n->tl;
-    if (second && d.residual) { a.Rhi = n->hh[cur]; a.Rlo = n->hl[cur]; }
-    a.bias = a.pt == 2 ? L.bx : L.b;
-    a.M = B * n->HW; a.N = d.channels; a.C = d.channels; a.H = d.board_size; a.W = d.board_size;
+    a.M = B * n->HW; a.N = n->d.channels; a.C = C; a.H = n->d.board_size; a.W = n->d.board_size;
     a.m_limit = nb; a.rows_per_sample = n->HW; a.relu = 1;
     a.a_tail = n->act_elems * 2;
     a.zero = n->zero; a.ovf = n->ovf;
     a.stamp = -1;
     return a;
 }
-// true when an AZ_PREC_BF16X3 net runs its trunk on conv3x3_v7x3 (else the NHWC split path,
-// conv3x3_v4<0>): decided by the shapes alone (the chunk-blocked hi / lo weights exist for every
-// 3x3 layer of a net with channels % 32 == 0 once it is loaded)
-bool x3_trunk(const az_net* n) {
-    const az_net_desc& d = n->d;
-    if (n->rw || (d.precision != AZ_PREC_BF16X3 && d.precision != AZ_PREC_F16X3) || d.blocks < 1 || !n->hh[0] ||
-        d.channels % 32)
-        return false;
-    Layer probe;
-    probe.Wbk_bf = probe.Wbk_lo = probe.Wbk_fh = probe.Wbk_fl = n->zero;   // stand-ins for the shape check
-    probe.sx = reinterpret_cast<float*>(n->zero);
-    return az_conv_v7x3_supported(x3_conv_args(n, probe, 1, 0, d.max_batch, nullptr));
+
+// K slices for an FC layer of B rows: enough blocks to cover the chip (a 128 x 128 f32 tile is
+// bound by the CU's f32 MFMA rate), slices of >= 64 K
+constexpr int FC_MAX_SPLITS = 64;
+int fc_splits(int B, int K) {
+    const int tiles = (B + 127) / 128 * 2;
+    int s = 1;
+    while (s < FC_MAX_SPLITS && tiles * s < 512 && K / (2 * s) >= 64) s *= 2;
+    return s;
 }
 
 }  // namespace
 
-int net_input_path(const az_net* n) {
-    const az_net_desc& d = n->d;
-    const int H = d.board_size, F = d.channels, prec = d.precision;
-    if (n->rw) return NET_IN_GEMM;   // rand-wire: f32 input conv on x0
-    if (n->sm_W && (prec == AZ_PREC_FP16 || prec == AZ_PREC_BF16X3 || prec == AZ_PREC_F16X3) && d.blocks > 0)
-        return NET_IN_SMALL;
-    const bool bf = (prec == AZ_PREC_BF16 || prec == AZ_PREC_FP16) && F % 32 == 0;
-    if (bf && az_conv_g8_supported(H, H, F, F) &&
-        ((n->in.Wbk_h != nullptr && az_conv_g8_supported(H, H, n->cin_pad, F)) || n->in32.Wbk_h != nullptr))
-        return NET_IN_G8;
-    return NET_IN_GEMM;
-}
+int net_input_path(const az_net* n) { return plan_of(n).input; }
 
 namespace {
 
 // Router of a rand-wire node: relu(BN(conv1x1(concat(ins)))) as ONE GEMM over K = deg F whose
 // k-slice j is read straight from input j's buffer (the device table `dins`, same k order as the
 // reference's torch::cat); BN folded into the weights and bias.
-void rw_router(const az_net* n, const Layer& L, const float* const* dins, float* out, int rows, const int* nb,
+void rw_router(const az_net* n, int trunk, const Layer& L, const float* const* dins, float* out, int rows, const int* nb,
                hipStream_t st) {
     const int F = n->d.channels, H = n->d.board_size;
     GemmArgs p{};
     p.Am = dins; p.lda = F; p.B = L.W; p.ldb = L.K; p.C = out; p.ldc = F; p.bias = L.b;
     p.M = rows; p.N = F; p.K = L.K; p.Kpad = L.Kpad; p.taps = 1; p.Cch = F; p.H = H; p.W = H;
     p.m_limit = nb; p.rows_per_sample = n->HW;
-    if (n->d.precision == AZ_PREC_FP16) az_launch_gemm_h16_relu(p, st);   // fp16 operands, fp32 accumulation
+    if (trunk == NET_TRUNK_RW_V4_FP16) az_launch_gemm_h16_relu(p, st);   // fp16 operands, fp32 accumulation
     else az_launch_gemm_f32(p, ACT_RELU, false, st);
 }
 
 // DDW-RandWire trunk (ddw_randwire_resnet.cpp:321-384 per block): input nodes on the block input,
 // the others in topological order on their router's output (or their single predecessor's
 // output), the block output (output router or the single sink) into the h0 / h1 ping-pong.
-float* rw_trunk(az_net* n, int B, const int* nb, hipStream_t st) {
+float* trunk_rw(az_net* n, int trunk, int B, const int* nb, hipStream_t st) {
     const az_net_desc& d = n->d;
     const int F = d.channels, H = d.board_size, HW = n->HW, rows = B * HW, R = F / 16;
     float* x = n->h0;
@@ -114,46 +83,33 @@ float* rw_trunk(az_net* n, int B, const int* nb, hipStream_t st) {
         const azrw::Plan& pl = blk.plan;
         auto node = [&](int v, const float* in) {
             const RwNode& nd = blk.node[v];
-            if (d.precision == AZ_PREC_FP16) {
-                // fp16 operands, fp32 accumulation (conv3x3_v4): conv1 -> fp16 t, conv2 -> fp32 y;
-                // the residual stream, routers and SE stay fp32
-                az_launch_to_f16(in, n->hh[0], (size_t)rows * F, nb, HW, F, st, n->ovf);
-                ConvBf16Args a{};
-                a.Ahi = n->hh[0]; a.Bhi = nd.c1.Wh16; a.Bblk = nd.c1.Wbk_h; a.Chi = n->th; a.bias = nd.c1.b;
-                a.M = rows; a.N = F; a.C = F; a.H = H; a.W = H; a.m_limit = nb; a.rows_per_sample = HW; a.relu = 1;
-                a.zero = n->zero; a.ovf = n->ovf; a.stamp = -1;
-                az_conv_v4_launch(a, 2, st);
+            if (trunk == NET_TRUNK_RW_F32) {
+                GemmArgs g1 = gemm_args(nd.c1, in, F, n->t, F, nullptr, rows, H, H, nb, HW);
+                GemmArgs g2 = gemm_args(nd.c2, n->t, F, n->rw_t2, F, nullptr, rows, H, H, nb, HW);
+                if (n->rw_ws) { g1.part = g2.part = n->rw_ws; g1.splits = g2.splits = n->rw_splits; }
+                az_launch_gemm_f32(g1, ACT_RELU, false, st);
+                az_launch_gemm_f32(g2, ACT_NONE, false, st);
+            } else {
+                // conv3x3_v4: conv1 -> 16-bit t, conv2 -> fp32 y; the residual stream, routers and SE stay
+                // fp32.  fp16 operands (mode 2), or fp32-faithful: operands split into bf16 hi + lo, three
+                // MFMAs per product (mode 0); fp32 accumulation in both
+                const bool x3 = trunk == NET_TRUNK_RW_V4_X3;
+                if (x3) az_launch_split_bf16(in, n->hh[0], n->hl[0], (size_t)rows * F, nb, HW, F, st);
+                else az_launch_to_f16(in, n->hh[0], (size_t)rows * F, nb, HW, F, st, n->ovf);
+                ConvBf16Args a = conv_args(n, B, nb, F);
+                a.Ahi = n->hh[0]; a.Chi = n->th; a.bias = nd.c1.b;
                 ConvBf16Args c = a;
-                c.Ahi = n->th; c.Bhi = nd.c2.Wh16; c.Bblk = nd.c2.Wbk_h; c.Chi = n->hh[1]; c.Cf = n->rw_t2; c.bias = nd.c2.b;
-                c.relu = 0;
-                az_conv_v4_launch(c, 2, st);
-                az_launch_se_residual(n->rw_t2, in, n->rw_out[v], nd.w1, nd.b1, nd.w2, nd.b2, B, HW, F, R, nb, st);
-                return;
+                c.Ahi = n->th; c.Chi = n->hh[1]; c.Cf = n->rw_t2; c.bias = nd.c2.b; c.relu = 0;
+                if (x3) {
+                    a.Alo = n->hl[0]; a.Bhi = nd.c1.Whi; a.Blo = nd.c1.Wlo; a.Bblk = nd.c1.Wbk_bf; a.Clo = n->tl;
+                    c.Alo = n->tl; c.Bhi = nd.c2.Whi; c.Blo = nd.c2.Wlo; c.Bblk = nd.c2.Wbk_bf; c.Clo = n->hl[1];
+                } else {
+                    a.Bhi = nd.c1.Wh16; a.Bblk = nd.c1.Wbk_h;
+                    c.Bhi = nd.c2.Wh16; c.Bblk = nd.c2.Wbk_h;
+                }
+                az_conv_v4_launch(a, x3 ? 0 : 2, st);
+                az_conv_v4_launch(c, x3 ? 0 : 2, st);
             }
-            if (d.precision == AZ_PREC_BF16X3 && d.max_batch >= 128) {
-                // fp32-faithful: operands split into bf16 hi + lo, three MFMAs per product, fp32
-                // accumulation (conv3x3_v4 mode 0); conv1 -> split t, conv2 -> fp32 y.  Below 128
-                // boards of capacity v4 has too few tiles (one per two boards) and the K-split f32
-                // GEMM below is faster (chosen by capacity: batch-size independent)
-                az_launch_split_bf16(in, n->hh[0], n->hl[0], (size_t)rows * F, nb, HW, F, st);
-                ConvBf16Args a{};
-                a.Ahi = n->hh[0]; a.Alo = n->hl[0]; a.Bhi = nd.c1.Whi; a.Blo = nd.c1.Wlo; a.Bblk = nd.c1.Wbk_bf;
-                a.Chi = n->th; a.Clo = n->tl; a.bias = nd.c1.b;
-                a.M = rows; a.N = F; a.C = F; a.H = H; a.W = H; a.m_limit = nb; a.rows_per_sample = HW; a.relu = 1;
-                a.zero = n->zero; a.ovf = n->ovf; a.stamp = -1;
-                az_conv_v4_launch(a, 0, st);
-                ConvBf16Args c = a;
-                c.Ahi = n->th; c.Alo = n->tl; c.Bhi = nd.c2.Whi; c.Blo = nd.c2.Wlo; c.Bblk = nd.c2.Wbk_bf;
-                c.Chi = n->hh[1]; c.Clo = n->hl[1]; c.Cf = n->rw_t2; c.bias = nd.c2.b; c.relu = 0;
-                az_conv_v4_launch(c, 0, st);
-                az_launch_se_residual(n->rw_t2, in, n->rw_out[v], nd.w1, nd.b1, nd.w2, nd.b2, B, HW, F, R, nb, st);
-                return;
-            }
-            GemmArgs g1 = gemm_args(nd.c1, in, F, n->t, F, nullptr, rows, H, H, nb, HW);
-            GemmArgs g2 = gemm_args(nd.c2, n->t, F, n->rw_t2, F, nullptr, rows, H, H, nb, HW);
-            if (n->rw_ws) { g1.part = g2.part = n->rw_ws; g1.splits = g2.splits = n->rw_splits; }
-            az_launch_gemm_f32(g1, ACT_RELU, false, st);
-            az_launch_gemm_f32(g2, ACT_NONE, false, st);
             az_launch_se_residual(n->rw_t2, in, n->rw_out[v], nd.w1, nd.b1, nd.w2, nd.b2, B, HW, F, R, nb, st);
         };
         for (int v : pl.inputs) node(v, x);
@@ -161,12 +117,12 @@ float* rw_trunk(az_net* n, int B, const int* nb, hipStream_t st) {
             const auto& pr = pl.preds[v];
             if (pr.empty() || std::find(pl.inputs.begin(), pl.inputs.end(), v) != pl.inputs.end()) continue;
             if (pr.size() == 1) { node(v, n->rw_out[pr[0]]); continue; }
-            rw_router(n, blk.node[v].router, blk.node[v].ins, n->rw_in, rows, nb, st);
+            rw_router(n, trunk, blk.node[v].router, blk.node[v].ins, n->rw_in, rows, nb, st);
             node(v, n->rw_in);
         }
         float* y = x == n->h0 ? n->h1 : n->h0;
         if (pl.outputs.size() > 1) {
-            rw_router(n, blk.out_router, blk.outs, y, rows, nb, st);
+            rw_router(n, trunk, blk.out_router, blk.outs, y, rows, nb, st);
         } else {
             (void)hipMemcpyAsync(y, n->rw_out[pl.outputs[0]], (size_t)rows * F * 4, hipMemcpyDeviceToDevice, st);
         }
@@ -179,8 +135,8 @@ float* rw_trunk(az_net* n, int B, const int* nb, hipStream_t st) {
 // net (not the zeroed tails, not the weights) is filled with that byte before each forward, so a
 // kernel that reads memory its forward never wrote gives a result that depends on the byte
 // (0xff: NaN in every float format) -- the tests compare forwards under two poisons bitwise
-static int g_poison = -1;
-static int poison_net(az_net* n, hipStream_t st, bool inputs) {
+int g_poison = -1;
+int poison_net(az_net* n, hipStream_t st, bool inputs) {
     if (g_poison < 0) return 0;
     for (const auto& b : n->scratch) {
         const bool in = b.first == (void*)n->x0 || b.first == (void*)n->in_nchw;
@@ -191,14 +147,13 @@ static int poison_net(az_net* n, hipStream_t st, bool inputs) {
 
 // The FC layers of both heads from the head feature maps pp / vp ([B][P*P][HC]; cell stride xs,
 // default HC: pp / vp may be the two halves of the combined head-conv output).
-int net_heads_fc(az_net* n, int B, const int* nb, float* logits, float* value, hipStream_t st, const float* pp,
-                 const float* vp, int xs) {
+int net_heads_fc(az_net* n, const NetPlan& pl, int B, const int* nb, float* logits, float* value, hipStream_t st,
+                 const float* pp = nullptr, const float* vp = nullptr, int xs = 0) {
     const az_net_desc& d = n->d;
-    const int PP = n->P2;
-    const int HK = d.head_channels * PP;
+    const int HK = d.head_channels * n->P2;
     if (!pp) { pp = n->pp; vp = n->vp; xs = d.head_channels; }
     // Both FC heads: k_fc_heads (split-K partials of both FCs in one GEMM) + k_fc_finish (per board)
-    if (HK % 32 == 0 && HK % 4 == 0) {
+    if (pl.heads != NET_HEADS_GENERIC) {
         FcHeadArgs fa{};
         fa.pp = pp; fa.vp = vp; fa.hc = d.head_channels; fa.xs = xs;
         fa.Wp = n->pfc.W; fa.bp = n->pfc.b; fa.Wv1 = n->vfc1.W; fa.bv1 = n->vfc1.b; fa.wv2 = n->vfc2.W; fa.bv2 = n->vfc2.b;
@@ -206,21 +161,10 @@ int net_heads_fc(az_net* n, int B, const int* nb, float* logits, float* value, h
         fa.part = n->ws; fa.m_limit = nb;
         fa.B = B; fa.K = HK; fa.A = d.action_size; fa.H = d.fc_hidden;
         fa.S = az_fc_heads_splits(d.max_batch, HK, d.action_size, d.fc_hidden);   // from the capacity: batch-size independent
-        // split-operand FC products at 5x the f32 MFMA rate: the throughput precisions (fp16 / bf16
-        // trunk) in bf16 pieces (~2^-16 per product; their trunk error is 30x larger), AZ_PREC_F16X3 in
-        // scaled fp16 pieces (~2^-21, as its trunk).  AZ_PREC_BF16X3 and F32 keep exact f32 products
-        // (bf16 pieces would add ~2.5e-5 at trained-scale logits).  Conv flag 0x08000000 keeps the f32
-        // k_fc_heads (A/B, diagnosis).
-        // Below 512 boards of capacity the f32 pair is the faster one (C2, 256 boards: k_fc_heads 10.6 us
-        // vs k_fc_heads_x3 12.0 -- both latency-bound chains of L2 round trips at 0.5 GFLOP).
-        const bool fx = !(az_conv_flags() & 0x08000000) && n->fcx_hi && d.max_batch >= 512;
-        if (fx && (d.precision == AZ_PREC_FP16 || d.precision == AZ_PREC_BF16)) {
-            fa.Wx_hi = n->fcx_hi; fa.Wx_lo = n->fcx_lo; fa.pt = 1;
-            fa.S = az_fc_heads_splits_x3(d.max_batch, HK, d.action_size, d.fc_hidden);
-        } else if (fx && d.precision == AZ_PREC_F16X3) {
-            fa.Wx_hi = n->fcf_hi; fa.Wx_lo = n->fcf_lo; fa.pt = 2; fa.rs = n->fcf_rs; fa.ovf = n->ovf;
-            fa.S = az_fc_heads_splits_x3(d.max_batch, HK, d.action_size, d.fc_hidden);
-        }
+        // the split-operand products (k_fc_heads_x3) where the plan takes them
+        if (pl.heads == NET_HEADS_X3_BF16) { fa.Wx_hi = n->fcx_hi; fa.Wx_lo = n->fcx_lo; fa.pt = 1; }
+        if (pl.heads == NET_HEADS_X3_FP16) { fa.Wx_hi = n->fcf_hi; fa.Wx_lo = n->fcf_lo; fa.pt = 2; fa.rs = n->fcf_rs; fa.ovf = n->ovf; }
+        if (fa.pt) fa.S = az_fc_heads_splits_x3(d.max_batch, HK, d.action_size, d.fc_hidden);
         az_launch_fc_heads(fa, st);
         HIPCHK(hipGetLastError());
         return 0;
@@ -241,236 +185,224 @@ int net_heads_fc(az_net* n, int B, const int* nb, float* logits, float* value, h
     return 0;
 }
 
+// Profiling: counts the forward (in trunk-conv equivalents: bench.py's per-conv rate) and, on a
+// sampled one, stamps the trunk's start; true when the closing stamp is due behind the trunk.
+bool prof_open(az_net* n, hipStream_t st) {
+    if (!n->prof || n->d.blocks < 1) return false;
+    n->prof_launches += 2 * n->d.blocks;
+    n->prof_forwards += 1;
+    if (n->prof_tick++ % prof_every() != 0 || !n->pc.room(2)) return false;
+    n->prof_sampled += 1;
+    n->pc.stamp(st);
+    return true;
+}
+
+// NET_TRUNK_SMALL: input conv, trunk, pool and the two head 1x1 convs in one launch (smallnet.hip)
+int forward_small(az_net* n, const NetPlan& pl, const float* x0, int B, const int* nb, float* logits, float* value,
+                  hipStream_t st, const LeafRecs* lr) {
+    const az_net_desc& d = n->d;
+    const bool sampled = prof_open(n, st);
+    SmallNetArgs sa{};
+    sa.x0 = x0; sa.m_limit = nb; sa.ovf = n->ovf;
+    if (lr) {
+        if (lr->go) return az_fail(AZ_ERR_ARG, "smallnet: Gomoku leaf records only");
+        sa.x0 = nullptr; sa.rec = lr->rec; sa.gidx = lr->gidx; sa.rec_n = lr->n; sa.rec_identity = lr->identity;
+    }
+    sa.W = n->sm_W; sa.Wf = n->sm_Wf; sa.bias = n->sm_b;
+    if (d.precision == AZ_PREC_BF16X3) { sa.Wxh = n->sm_Wxh; sa.Wxl = n->sm_Wxl; sa.pt = 1; }   // k_smallnet_x3
+    if (d.precision == AZ_PREC_F16X3) {
+        sa.Wxh = n->sm_Wfh; sa.Wxl = n->sm_Wfl; sa.pt = 2; sa.bias = n->sm_bx; sa.osc = n->sm_sx;
+    }
+    sa.Wpc = n->pconv.W; sa.bpc = n->pconv.b; sa.Wvc = n->vconv.W; sa.bvc = n->vconv.b;
+    sa.pp = n->pp; sa.vp = n->vp;
+    sa.H = d.board_size; sa.blocks = d.blocks; sa.residual = d.residual; sa.HC = d.head_channels; sa.P = d.pool;
+    sa.stamps = az_smallnet_stamps_mode();   // diagnostic phase stamps (az_diag_set_smallnet_stamps)
+    if (az_smallnet_launch(sa, B, st)) return az_fail(AZ_ERR_ARG, "smallnet: unsupported shape");
+    if (sampled) n->pc.stamp(st);
+    return net_heads_fc(n, pl, B, nb, logits, value, st);
+}
+
+// The int8 remainder planes of the g8 trunk live in the (otherwise idle) lo buffers
+int8_t* g8_q(const az_net* n, int i) { return reinterpret_cast<int8_t*>(n->hl[i]); }
+
+// NET_IN_G8: input planes -> g8 16-bit in th (0/1 planes are exact), then the input conv on the g8
+// kernel into hh[0]; plan.in32: the planes as 32 channels (groups 2-3 zero) for the zero-padded layer
+int input_g8(az_net* n, const NetPlan& pl, const float* x0, int B, const int* nb, hipStream_t st, const LeafRecs* lr) {
+    const bool f16 = n->d.precision == AZ_PREC_FP16;
+    const int mode = f16 ? 2 : 1, H = n->d.board_size;
+    const Layer& IN = pl.in32 ? n->in32 : n->in;
+    const int cin = pl.in32 ? 32 : n->cin_pad;
+    if (lr) {
+        if (n->cin_pad != 16) return az_fail(AZ_ERR_ARG, "leaf records carry 16 planes");
+        az_launch_rec_to_g8(lr->rec, lr->gidx, n->th, lr->go, H, nb, B, mode, st, cin / 8);
+    } else {
+        az_launch_to_g8(x0, n->th, nullptr, n->cin_pad, n->HW, nb, B, mode, st, cin);
+    }
+    ConvBf16Args a = conv_args(n, B, nb, cin);
+    a.Ahi = n->th; a.Bblk = f16 ? IN.Wbk_h : IN.Wbk_bf; a.bias = IN.b;
+    a.Chi = n->hh[0]; a.Cq = g8_q(n, 0);
+    if (az_conv_g8_launch(a, mode, st)) return az_fail(AZ_ERR_ARG, "g8 input conv: unsupported shape");
+    return 0;
+}
+
+// NET_TRUNK_GEMM_F32: the fp32 NHWC stream from h0; returns the trunk's output
+float* trunk_gemm_f32(az_net* n, int B, const int* nb, hipStream_t st) {
+    const az_net_desc& d = n->d;
+    const int H = d.board_size, F = d.channels, HW = n->HW, rows = B * HW;
+    float *h = n->h0, *other = n->h1;
+    for (int i = 0; i < d.blocks; ++i) {
+        az_launch_gemm_f32(gemm_args(n->blk[2 * i], h, F, n->t, F, nullptr, rows, H, H, nb, HW), ACT_RELU, false, st);
+        az_launch_gemm_f32(gemm_args(n->blk[2 * i + 1], n->t, F, other, F, d.residual ? h : nullptr, rows, H, H, nb, HW),
+                           ACT_RELU, d.residual != 0, st);
+        std::swap(h, other);
+    }
+    return h;
+}
+
+// NET_TRUNK_G8X3, the fp32-faithful trunk: every activation as g8 hi + lo planes (bf16 or fp16
+// pieces), three MFMAs per product (conv3x3_v9x3 / v7x3).  From the fp32 h0 to the planes hh / hl[*cur].
+int trunk_g8x3(az_net* n, int B, const int* nb, hipStream_t st, int* cur) {
+    const az_net_desc& d = n->d;
+    const int F = d.channels, pt = d.precision == AZ_PREC_F16X3 ? 2 : 1;
+    az_launch_to_g8x3(n->h0, n->hh[0], n->hl[0], F, n->HW, nb, B, st, pt, n->ovf);
+    int c = 0;
+    for (int i = 0; i < 2 * d.blocks; ++i) {
+        const Layer& L = n->blk[i];
+        const bool second = i & 1;
+        ConvBf16Args a = conv_args(n, B, nb, F);
+        a.Ahi = second ? n->th : n->hh[c]; a.Alo = second ? n->tl : n->hl[c];
+        a.Bblk = L.Wbk_bf; a.Bblk_lo = L.Wbk_lo; a.bias = L.b; a.pt = pt;
+        if (pt == 2) { a.Bblk = L.Wbk_fh; a.Bblk_lo = L.Wbk_fl; a.oscale = L.sx; a.bias = L.bx; }
+        a.Chi = second ? n->hh[c ^ 1] : n->th; a.Clo = second ? n->hl[c ^ 1] : n->tl;
+        if (second && d.residual) { a.Rhi = n->hh[c]; a.Rlo = n->hl[c]; }
+        a.stamp = i;
+        if (az_conv_v7x3_launch(a, st)) return az_fail(AZ_ERR_ARG, "bf16x3 trunk conv: unsupported shape");
+        if (second) c ^= 1;
+    }
+    *cur = c;
+    return 0;
+}
+
+// NET_TRUNK_G8: 16-bit g8 planes with int8 remainders (conv3x3_v5 / v6 / v7 by the launch), from
+// the input conv's hh[0] to the planes hh[*cur] / g8_q(*cur)
+int trunk_g8(az_net* n, int B, const int* nb, hipStream_t st, int* cur) {
+    const az_net_desc& d = n->d;
+    const bool f16 = d.precision == AZ_PREC_FP16;
+    int c = 0;
+    for (int i = 0; i < 2 * d.blocks; ++i) {
+        const Layer& L = n->blk[i];
+        const bool second = i & 1;
+        ConvBf16Args a = conv_args(n, B, nb, d.channels);
+        a.Ahi = second ? n->th : n->hh[c];
+        a.Bblk = f16 ? L.Wbk_h : L.Wbk_bf; a.bias = L.b;
+        a.Chi = second ? n->hh[c ^ 1] : n->th;
+        if (second) a.Cq = g8_q(n, c ^ 1);
+        if (second && d.residual) { a.Rhi = n->hh[c]; a.Rq = g8_q(n, c); }
+        a.stamp = i;
+        if (az_conv_g8_launch(a, f16 ? 2 : 1, st)) return az_fail(AZ_ERR_ARG, "g8 trunk conv: unsupported shape");
+        if (second) c ^= 1;
+    }
+    *cur = c;
+    return 0;
+}
+
+// NET_TRUNK_NHWC16: 16-bit NHWC operands from the fp32 h0 -- bf16 (conv3x3_v4 / v3 / conv3x3_bf16),
+// bf16 hi + lo (AZ_PREC_BF16X3 off the g8 boards) or fp16 (conv3x3_v4) with the fp32 residual
+// stream; returns the trunk's fp32 output
+float* trunk_nhwc16(az_net* n, int B, const int* nb, hipStream_t st) {
+    const az_net_desc& d = n->d;
+    const int F = d.channels, HW = n->HW, rows = B * HW;
+    const bool f16 = d.precision == AZ_PREC_FP16, split = d.precision == AZ_PREC_BF16X3;
+    float *h = n->h0, *other = n->h1;
+    if (f16) az_launch_to_f16(h, n->hh[0], (size_t)rows * F, nb, HW, F, st, n->ovf);
+    else az_launch_split_bf16(h, n->hh[0], split ? n->hl[0] : nullptr, (size_t)rows * F, nb, HW, F, st);
+    int cur = 0;
+    for (int i = 0; i < d.blocks; ++i) {
+        const Layer& L1 = n->blk[2 * i];
+        const Layer& L2 = n->blk[2 * i + 1];
+        ConvBf16Args a = conv_args(n, B, nb, F);
+        a.Ahi = n->hh[cur]; a.Bhi = f16 ? L1.Wh16 : L1.Whi; a.Bblk = f16 ? L1.Wbk_h : L1.Wbk_bf;
+        a.Chi = n->th; a.bias = L1.b;
+        if (split) { a.Alo = n->hl[cur]; a.Blo = L1.Wlo; a.Clo = n->tl; }
+        a.stamp = 2 * i;
+        ConvBf16Args b2 = a;
+        b2.Ahi = n->th; b2.Bhi = f16 ? L2.Wh16 : L2.Whi; b2.Bblk = f16 ? L2.Wbk_h : L2.Wbk_bf;
+        b2.Chi = n->hh[cur ^ 1]; b2.bias = L2.b;
+        if (split) { b2.Alo = n->tl; b2.Blo = L2.Wlo; b2.Clo = n->hl[cur ^ 1]; }
+        b2.stamp = 2 * i + 1;
+        if (f16) {
+            // fp16 conv operands, fp32 residual stream (an fp16 stream doubles the logit error)
+            b2.Rf = d.residual ? h : nullptr;
+            b2.Cf = other;
+            az_conv_v4_launch(a, 2, st);
+            az_conv_v4_launch(b2, 2, st);
+            std::swap(h, other);
+        } else {
+            if (d.residual) { b2.Rhi = n->hh[cur]; b2.Rlo = split ? n->hl[cur] : nullptr; }
+            b2.Cf = (i == d.blocks - 1) ? other : nullptr;
+            az_conv_bf16_launch_v(a, split, st);
+            az_conv_bf16_launch_v(b2, split, st);
+        }
+        cur ^= 1;
+    }
+    return d.blocks > 0 && !f16 ? other : h;
+}
+
 }  // namespace
 
 // Forward of B samples (B = capacity; *nb = active samples, device side) from the
 // NHWC16 input x0 -> logits [B][A], value [B].  lr (optional; only where
 // net_input_path != NET_IN_GEMM): the planes come from leaf records instead of x0.
+// Three stages on the net's plan: the input stage, one function per trunk family, the tail.
 int net_forward(az_net* n, const float* x0, int B, const int* nb, float* logits, float* value, hipStream_t st,
                 const LeafRecs* lr) {
     const az_net_desc& d = n->d;
-    const int H = d.board_size, W = d.board_size, HW = n->HW, F = d.channels, P = d.pool, PP = n->P2;
-    const int rows = B * HW;
-    const int prec = d.precision;
-    const bool bf = (prec == AZ_PREC_BF16X3 || prec == AZ_PREC_F16X3 || prec == AZ_PREC_BF16 || prec == AZ_PREC_FP16) &&
-                    F % 32 == 0;
-    const bool f16 = prec == AZ_PREC_FP16;
-    const bool x3 = prec == AZ_PREC_BF16X3 || prec == AZ_PREC_F16X3;
-    // g8 path (v5 / v6 conv, fp16/bf16): input conv, trunk and pool all on 16-bit channel-blocked rows
-    const bool g8 = !n->rw && bf && !x3 && az_conv_g8_supported(H, W, F, F);
-    const bool g8x3 = x3_trunk(n);   // AZ_PREC_BF16X3 / F16X3 on the g8 hi / lo planes
-    const int mode = f16 ? 2 : 1;
-    int8_t* hq[2] = {reinterpret_cast<int8_t*>(n->hl[0]), reinterpret_cast<int8_t*>(n->hl[1])};
-    const int inpath = net_input_path(n);
-    // the trunk's tail -- pool and both head 1x1 convs -- in one launch on the g8 paths
-    // (k_pool_heads_g8, bitwise what k_pool_g8 + gemm_f32 give; conv flag 0x400000 keeps those for A/B)
-    const bool tail_fused = (g8 || g8x3) && n->hpv && (d.head_channels * PP) % 32 == 0 &&
-                            az_pool_heads_supported(F, H, P, 2 * d.head_channels) && !(az_conv_flags() & 0x400000);
-    if (lr && inpath == NET_IN_GEMM) return az_fail(AZ_ERR_ARG, "net_forward: this net cannot read leaf records");
+    const int H = d.board_size, HW = n->HW, F = d.channels, P = d.pool, PP = n->P2, HC = d.head_channels;
+    const NetPlan pl = plan_of(n);
+    if (lr && pl.input == NET_IN_GEMM) return az_fail(AZ_ERR_ARG, "net_forward: this net cannot read leaf records");
     if (int r = poison_net(n, st, false)) return r;
-    if (prec == AZ_PREC_F16X3 && !g8x3 && inpath != NET_IN_SMALL)
-        return az_fail(AZ_ERR_ARG, "AZ_PREC_F16X3: no fp16-piece trunk for this shape");
-    if (inpath == NET_IN_SMALL) {
-        // one launch: input conv, trunk, pool and the two head 1x1 convs (smallnet.hip)
-        bool sampled = false;
-        if (n->prof) {
-            n->prof_launches += 2 * d.blocks;    // counted in trunk-conv equivalents (bench.py's per-conv rate)
-            n->prof_forwards += 1;
-        }
-        if (n->prof && n->prof_tick++ % prof_every() == 0 && n->pc.room(2)) {
-            n->prof_sampled += 1;
-            sampled = true;
-            n->pc.stamp(st);
-        }
-        SmallNetArgs sa{};
-        sa.x0 = x0; sa.m_limit = nb; sa.ovf = n->ovf;
-        if (lr) {
-            if (lr->go) return az_fail(AZ_ERR_ARG, "smallnet: Gomoku leaf records only");
-            sa.x0 = nullptr; sa.rec = lr->rec; sa.gidx = lr->gidx; sa.rec_n = lr->n; sa.rec_identity = lr->identity;
-        } sa.W = n->sm_W; sa.Wf = n->sm_Wf; sa.bias = n->sm_b;
-        if (prec == AZ_PREC_BF16X3) { sa.Wxh = n->sm_Wxh; sa.Wxl = n->sm_Wxl; sa.pt = 1; }   // k_smallnet_x3
-        if (prec == AZ_PREC_F16X3) {
-            sa.Wxh = n->sm_Wfh; sa.Wxl = n->sm_Wfl; sa.pt = 2; sa.bias = n->sm_bx; sa.osc = n->sm_sx;
-        }
-        sa.Wpc = n->pconv.W; sa.bpc = n->pconv.b; sa.Wvc = n->vconv.W; sa.bvc = n->vconv.b;
-        sa.pp = n->pp; sa.vp = n->vp;
-        sa.H = H; sa.blocks = d.blocks; sa.residual = d.residual; sa.HC = d.head_channels; sa.P = P;
-        sa.stamps = az_smallnet_stamps_mode();   // diagnostic phase stamps (az_diag_set_smallnet_stamps)
-        if (az_smallnet_launch(sa, B, st)) return az_fail(AZ_ERR_ARG, "smallnet: unsupported shape");
-        if (sampled) n->pc.stamp(st);
-        return net_heads_fc(n, B, nb, logits, value, st);
-    }
-    if (inpath == NET_IN_G8) {
-        // input planes -> g8 16-bit (0/1 planes are exact), then the input conv on the g8 kernel; 16
-        // planes on a board whose g8 conv needs 32-channel chunks: zero groups 2-3 and in32
-        // (15x15 keeps 16 channels on conv3x3_v5: 126 us per 2048-board launch against 146 us for
-        // conv3x3_v6 on the zero-padded 32, profiles/r05_fused_tail_ab.txt)
-        const bool i32 = !az_conv_g8_supported(H, W, n->cin_pad, F);
-        const Layer& IN = i32 ? n->in32 : n->in;
-        const int cin = i32 ? 32 : n->cin_pad;
-        if (lr) {
-            if (n->cin_pad != 16) return az_fail(AZ_ERR_ARG, "leaf records carry 16 planes");
-            az_launch_rec_to_g8(lr->rec, lr->gidx, n->th, lr->go, H, nb, B, mode, st, cin / 8);
-        } else {
-            az_launch_to_g8(x0, n->th, nullptr, n->cin_pad, HW, nb, B, mode, st, cin);
-        }
-        ConvBf16Args a{};
-        a.Ahi = n->th;
-        a.Bblk = f16 ? IN.Wbk_h : IN.Wbk_bf;
-        a.Chi = n->hh[0]; a.Cq = hq[0];
-        a.bias = IN.b;
-        a.M = rows; a.N = F; a.C = cin; a.H = H; a.W = W; a.m_limit = nb; a.rows_per_sample = HW; a.relu = 1;
-        a.a_tail = n->act_elems * 2;          // th's zeroed tail sits behind its full capacity
-        a.zero = n->zero; a.ovf = n->ovf;
-        a.stamp = -1;
-        if (az_conv_g8_launch(a, mode, st)) return az_fail(AZ_ERR_ARG, "g8 input conv: unsupported shape");
-    } else if (g8) {
-        // few input planes on a board v6 cannot take at 16 channels: f32 input conv, then to g8
-        az_launch_gemm_f32(gemm_args(n->in, x0, n->cin_pad, n->h0, F, nullptr, rows, H, W, nb, HW), ACT_RELU, false, st);
-        az_launch_to_g8(n->h0, n->hh[0], hq[0], F, HW, nb, B, mode, st);
+    if (pl.no_forward) return az_fail(AZ_ERR_ARG, "%s", pl.no_forward);
+    if (pl.trunk == NET_TRUNK_SMALL) return forward_small(n, pl, x0, B, nb, logits, value, st, lr);
+
+    if (pl.input == NET_IN_G8) {
+        if (int r = input_g8(n, pl, x0, B, nb, st, lr)) return r;
     } else {
-        az_launch_gemm_f32(gemm_args(n->in, x0, n->cin_pad, n->h0, F, nullptr, rows, H, W, nb, HW), ACT_RELU, false, st);
+        az_launch_gemm_f32(gemm_args(n->in, x0, n->cin_pad, n->h0, F, nullptr, B * HW, H, H, nb, HW), ACT_RELU, false, st);
     }
-    float* h = n->h0;
-    float* other = n->h1;
-    bool ev1 = false;                    // a sampled forward: the trunk's closing stamp is pending
-    if (n->prof && d.blocks > 0) {
-        n->prof_launches += 2 * d.blocks;
-        n->prof_forwards += 1;
+
+    const bool sampled = prof_open(n, st);
+    const bool g8 = pl.trunk == NET_TRUNK_G8 || pl.trunk == NET_TRUNK_G8X3;
+    float* h = nullptr;   // the trunk's output: fp32 NHWC, or on the g8 families the planes hh / hl[cur]
+    int cur = 0, r = 0;
+    switch (pl.trunk) {
+        case NET_TRUNK_G8: r = trunk_g8(n, B, nb, st, &cur); break;
+        case NET_TRUNK_G8X3: r = trunk_g8x3(n, B, nb, st, &cur); break;
+        case NET_TRUNK_NHWC16: h = trunk_nhwc16(n, B, nb, st); break;
+        case NET_TRUNK_GEMM_F32: h = trunk_gemm_f32(n, B, nb, st); break;
+        default: h = trunk_rw(n, pl.trunk, B, nb, st); break;
     }
-    if (n->prof && d.blocks > 0 && n->prof_tick++ % prof_every() == 0 && n->pc.room(2)) {
-        n->prof_sampled += 1;
-        ev1 = true;
-        n->pc.stamp(st);
-    }
-    if (n->rw) {
-        h = rw_trunk(n, B, nb, st);
-    } else if (!bf) {
-        for (int i = 0; i < d.blocks; ++i) {
-            az_launch_gemm_f32(gemm_args(n->blk[2 * i], h, F, n->t, F, nullptr, rows, H, W, nb, HW), ACT_RELU, false, st);
-            az_launch_gemm_f32(gemm_args(n->blk[2 * i + 1], n->t, F, other, F, d.residual ? h : nullptr, rows, H, W, nb, HW),
-                               ACT_RELU, d.residual != 0, st);
-            std::swap(h, other);
-        }
-    } else if (g8x3) {
-        // fp32-faithful trunk: every activation as g8 hi + lo planes (bf16 or fp16 pieces), three MFMAs
-        // per product
-        const int pt = prec == AZ_PREC_F16X3 ? 2 : 1;
-        az_launch_to_g8x3(h, n->hh[0], n->hl[0], F, HW, nb, B, st, pt, n->ovf);
-        int cur = 0;
-        for (int i = 0; i < d.blocks; ++i) {
-            ConvBf16Args a = x3_conv_args(n, n->blk[2 * i], 0, cur, B, nb);
-            a.stamp = 2 * i;
-            if (az_conv_v7x3_launch(a, st)) return az_fail(AZ_ERR_ARG, "bf16x3 trunk conv: unsupported shape");
-            ConvBf16Args b2 = x3_conv_args(n, n->blk[2 * i + 1], 1, cur, B, nb);
-            b2.stamp = 2 * i + 1;
-            if (az_conv_v7x3_launch(b2, st)) return az_fail(AZ_ERR_ARG, "bf16x3 trunk conv: unsupported shape");
-            cur ^= 1;
-        }
-        if (ev1) n->pc.stamp(st);
-        ev1 = false;
-        if (tail_fused) {
-            if (az_launch_pool_heads_g8(n->hh[cur], reinterpret_cast<const int8_t*>(n->hl[cur]), n->hconv.W, n->hconv.b,
-                                        n->hpv, B, F, H, P, 2 * d.head_channels, nb, pt == 2 ? 3 : 0, st))
-                return az_fail(AZ_ERR_HIP, "k_pool_heads_g8 launch failed");
-        } else {
-            az_launch_pool_g8(n->hh[cur], reinterpret_cast<const int8_t*>(n->hl[cur]), n->pool, B, F, H, P, nb,
-                              pt == 2 ? 3 : 0, st);
-        }
+    if (r) return r;
+    if (sampled) n->pc.stamp(st);
+
+    // the tail -- pool and both head 1x1 convs: one launch on the g8 paths (k_pool_heads_g8, bitwise
+    // what k_pool_g8 + gemm_f32 give)
+    if (g8) {
+        // k_pool_g8 modes: 1 bf16 / 2 fp16 planes + int8 remainders, 0 bf16 / 3 fp16 hi + lo planes
+        const int mode = pl.trunk == NET_TRUNK_G8 ? (d.precision == AZ_PREC_FP16 ? 2 : 1) : (d.precision == AZ_PREC_F16X3 ? 3 : 0);
+        if (!pl.tail_fused) az_launch_pool_g8(n->hh[cur], g8_q(n, cur), n->pool, B, F, H, P, nb, mode, st);
+        else if (az_launch_pool_heads_g8(n->hh[cur], g8_q(n, cur), n->hconv.W, n->hconv.b, n->hpv, B, F, H, P, 2 * HC, nb, mode, st))
+            return az_fail(AZ_ERR_HIP, "k_pool_heads_g8 launch failed");
     } else {
-        const bool split = prec == AZ_PREC_BF16X3;
-        if (g8) {
-            // g8 layout, v5 conv; the int8 remainder planes live in the (otherwise idle) bf16 lo buffers
-            int cur = 0;
-            for (int i = 0; i < d.blocks; ++i) {
-                const Layer& L1 = n->blk[2 * i];
-                const Layer& L2 = n->blk[2 * i + 1];
-                ConvBf16Args a{};
-                a.Ahi = n->hh[cur];
-                a.Bblk = f16 ? L1.Wbk_h : L1.Wbk_bf;
-                a.Chi = n->th;
-                a.bias = L1.b;
-                a.M = rows; a.N = F; a.C = F; a.H = H; a.W = W; a.m_limit = nb; a.rows_per_sample = HW; a.relu = 1;
-                a.a_tail = n->act_elems * 2;
-                a.zero = n->zero; a.ovf = n->ovf;
-                a.stamp = 2 * i;
-                if (az_conv_g8_launch(a, mode, st)) return az_fail(AZ_ERR_ARG, "g8 trunk conv: unsupported shape");
-                ConvBf16Args b2 = a;
-                b2.stamp = 2 * i + 1;
-                b2.Ahi = n->th;
-                b2.Bblk = f16 ? L2.Wbk_h : L2.Wbk_bf;
-                b2.Chi = n->hh[cur ^ 1]; b2.Cq = hq[cur ^ 1];
-                b2.bias = L2.b;
-                if (d.residual) { b2.Rhi = n->hh[cur]; b2.Rq = hq[cur]; }
-                if (az_conv_g8_launch(b2, mode, st)) return az_fail(AZ_ERR_ARG, "g8 trunk conv: unsupported shape");
-                cur ^= 1;
-            }
-            if (ev1) n->pc.stamp(st);
-            ev1 = false;
-            if (tail_fused) {
-                if (az_launch_pool_heads_g8(n->hh[cur], hq[cur], n->hconv.W, n->hconv.b, n->hpv, B, F, H, P,
-                                            2 * d.head_channels, nb, mode, st))
-                    return az_fail(AZ_ERR_HIP, "k_pool_heads_g8 launch failed");
-            } else {
-                az_launch_pool_g8(n->hh[cur], hq[cur], n->pool, B, F, H, P, nb, mode, st);
-            }
-        } else {
-        if (f16) az_launch_to_f16(h, n->hh[0], (size_t)rows * F, nb, HW, F, st, n->ovf);
-        else az_launch_split_bf16(h, n->hh[0], split ? n->hl[0] : nullptr, (size_t)rows * F, nb, HW, F, st);
-        int cur = 0;
-        for (int i = 0; i < d.blocks; ++i) {
-            const Layer& L1 = n->blk[2 * i];
-            const Layer& L2 = n->blk[2 * i + 1];
-            ConvBf16Args a{};
-            a.Ahi = n->hh[cur]; a.Alo = split ? n->hl[cur] : nullptr;
-            a.Bhi = L1.Whi; a.Blo = split ? L1.Wlo : nullptr;
-            a.Chi = n->th; a.Clo = split ? n->tl : nullptr; a.Cf = nullptr;
-            a.bias = L1.b; a.Rhi = nullptr; a.Rlo = nullptr;
-            a.M = rows; a.N = F; a.C = F; a.H = H; a.W = W; a.m_limit = nb; a.rows_per_sample = HW; a.relu = 1;
-            a.zero = n->zero; a.ovf = n->ovf;
-            a.stamp = 2 * i;
-            a.Bblk = f16 ? L1.Wbk_h : L1.Wbk_bf;
-            if (f16) a.Bhi = L1.Wh16;
-            if (f16) az_conv_v4_launch(a, 2, st);
-            else az_conv_bf16_launch_v(a, split, st);
-            ConvBf16Args b2 = a;
-            b2.Ahi = n->th; b2.Alo = split ? n->tl : nullptr;
-            b2.Bhi = L2.Whi; b2.Blo = split ? L2.Wlo : nullptr;
-            b2.Chi = n->hh[cur ^ 1]; b2.Clo = split ? n->hl[cur ^ 1] : nullptr;
-            b2.bias = L2.b;
-            b2.stamp = 2 * i + 1;
-            b2.Bblk = f16 ? L2.Wbk_h : L2.Wbk_bf;
-            b2.Rhi = d.residual ? n->hh[cur] : nullptr; b2.Rlo = d.residual && split ? n->hl[cur] : nullptr;
-            b2.Cf = (i == d.blocks - 1) ? other : nullptr;
-            if (f16) {
-                // fp16 conv operands, fp32 residual stream (an fp16 stream doubles the logit error)
-                b2.Bhi = L2.Wh16;
-                b2.Rhi = nullptr;
-                b2.Rf = d.residual ? h : nullptr;
-                b2.Cf = other;
-                az_conv_v4_launch(b2, 2, st);
-                std::swap(h, other);
-            } else {
-                az_conv_bf16_launch_v(b2, split, st);
-            }
-            cur ^= 1;
-        }
-        if (d.blocks > 0 && !f16) h = other;
-        }
+        az_launch_pool(h, n->pool, B, H, H, F, P, nb, st);
     }
-    if (ev1) n->pc.stamp(st);
-    if (!g8 && !g8x3) az_launch_pool(h, n->pool, B, H, W, F, P, nb, st);
-    const int HC = d.head_channels, HK = HC * PP;
-    if (tail_fused) return net_heads_fc(n, B, nb, logits, value, st, n->hpv, n->hpv + HC, 2 * HC);
-    if (HK % 32 == 0 && n->hpv) {
+    if (pl.head_conv_fused)
         // both head 1x1 convs as one GEMM (2 HC outputs; every output is the same k-ordered fp32
         // chain as in two launches), read by the FC heads with a 2 HC cell stride
         az_launch_gemm_f32(gemm_args(n->hconv, n->pool, F, n->hpv, 2 * HC, nullptr, B * PP, 1, 1, nb, PP), ACT_RELU, false, st);
-        return net_heads_fc(n, B, nb, logits, value, st, n->hpv, n->hpv + HC, 2 * HC);
-    }
+    if (pl.tail_fused || pl.head_conv_fused) return net_heads_fc(n, pl, B, nb, logits, value, st, n->hpv, n->hpv + HC, 2 * HC);
     az_launch_gemm_f32(gemm_args(n->pconv, n->pool, F, n->pp, HC, nullptr, B * PP, 1, 1, nb, PP), ACT_RELU, false, st);
     az_launch_gemm_f32(gemm_args(n->vconv, n->pool, F, n->vp, HC, nullptr, B * PP, 1, 1, nb, PP), ACT_RELU, false, st);
-    return net_heads_fc(n, B, nb, logits, value, st);
+    return net_heads_fc(n, pl, B, nb, logits, value, st);
 }
 
 // The fp16 range guard's flag of a net (sticky on the device until read here): AZ_ERR_RANGE once set.
@@ -482,30 +414,10 @@ int check_ovf(az_net* n, int ovf) {
                                  "use AZ_PREC_BF16X3 for nets with activations of this magnitude");
 }
 
-static int check_precision(const az_net_desc& d, int precision) {
-    if (precision < 0 || precision > 4) return az_fail(AZ_ERR_ARG, "bad precision %d", precision);
-    if (precision == AZ_PREC_F16X3) {
-        // the fp16-piece kernels: conv3x3_v9x3 / v7x3 (8/9/13/15/19 boards, channels % 128 == 0) or
-        // k_smallnet_x3 (15x15, 64 channels)
-        const int H = d.board_size;
-        // (the shape test of az_conv_v7x3_supported at the capacity, as x3_trunk applies it: the 32-bit
-        // buffer ranges of the activations + their zeroed tail and of the weights)
-        const size_t act_bytes = (size_t)d.max_batch * H * H * d.channels * 2;
-        const bool trunk = (H == 8 || H == 9 || H == 13 || H == 15 || H == 19) && d.channels % 128 == 0 &&
-                           act_bytes + AZ_ACT_TAIL * 2 < ((size_t)1 << 31) &&
-                           (size_t)9 * d.channels * d.channels * 2 < ((size_t)1 << 31);
-        const bool small = az_smallnet_supported(H, d.channels, (d.in_planes + 15) / 16 * 16, d.pool, d.head_channels) &&
-                           d.blocks <= az_smallnet_max_blocks();
-        if (!trunk && !small && d.blocks > 0)
-            return az_fail(AZ_ERR_ARG, "AZ_PREC_F16X3 needs an 8/9/13/15/19 board with channels %% 128 == 0 (and under 2 GiB "
-                                    "per activation buffer), or the 15x15 64-channel net; use AZ_PREC_BF16X3 or AZ_PREC_F32");
-    }
-    if (precision != AZ_PREC_F32 && d.channels % 32) return az_fail(AZ_ERR_ARG, "bf16/fp16 trunk needs channels %% 32 == 0");
-    if (precision == AZ_PREC_FP16 && !az_conv_v4_supported(d.board_size, d.board_size, d.channels, d.channels) &&
-        !az_conv_g8_supported(d.board_size, d.board_size, d.channels, d.channels))
-        return az_fail(AZ_ERR_ARG, "AZ_PREC_FP16 trunk needs 15x15 boards and channels %% 64 == 0, or an 8/9/13/15/19 board "
-                                "and channels %% 128 == 0");
-    return 0;
+// What az_net_create* / az_net_set_precision answer for a precision on this description: the plan's refusal
+static int check_precision(const az_net_desc& d, bool rw, int precision) {
+    const NetPlan pl = net_plan(net_shape(d, rw), precision, 0, 0);
+    return pl.status ? az_fail(pl.status, "%s", pl.message) : 0;
 }
 
 static int net_create(az_engine* e, const az_net_desc* d, az_net** out, bool rw,
@@ -516,7 +428,7 @@ static int net_create(az_engine* e, const az_net_desc* d, az_net** out, bool rw,
         d->head_channels < 1 || d->head_channels % 4 || d->pool < 1 || d->fc_hidden < 1 || d->fc_hidden % 4 ||
         d->max_batch < 1)
         return az_fail(AZ_ERR_ARG, "unsupported network description");
-    if (int r = check_precision(*d, d->precision)) return r;
+    if (int r = check_precision(*d, rw, d->precision)) return r;
     std::lock_guard<std::mutex> lk(e->mu);
     HIPCHK(hipSetDevice(e->device));
     auto* n = new az_net();
@@ -524,10 +436,7 @@ static int net_create(az_engine* e, const az_net_desc* d, az_net** out, bool rw,
     n->d = *d;
     n->HW = d->board_size * d->board_size;
     n->P2 = d->pool * d->pool;
-    // input channels padded to 16 (the search's plane records); more than 16 planes on a g8 board
-    // pad to 32 so the v6 conv takes the input layer as whole 32-channel chunks
-    n->cin_pad = (d->in_planes + 15) / 16 * 16;
-    if (n->cin_pad > 16 && d->channels % 128 == 0) n->cin_pad = (d->in_planes + 31) / 32 * 32;
+    n->cin_pad = net_shape(*d, rw).cin_pad;
     n->rw = rw;
     if (rw) {
         n->rwb.resize(d->blocks);
@@ -610,23 +519,11 @@ static int net_create(az_engine* e, const az_net_desc* d, az_net** out, bool rw,
 }
 
 
-// Rand-wire precisions: AZ_PREC_F32 (the reference module's arithmetic, any shape), or on 15x15
-// with channels % 64 == 0 the conv3x3_v4 node convs: AZ_PREC_BF16X3 (fp32-faithful split operands,
-// fp32 routers) or AZ_PREC_FP16 (fp16 operands, fp16-operand routers); SE and the residual stream
-// stay fp32 in every mode.
-static int check_rw_precision(const az_net_desc& d, int precision) {
-    if (precision == AZ_PREC_F32) return 0;
-    if ((precision == AZ_PREC_FP16 || precision == AZ_PREC_BF16X3) &&
-        az_conv_v4_supported(d.board_size, d.board_size, d.channels, d.channels))
-        return 0;
-    return az_fail(AZ_ERR_ARG, "rand-wire nets: AZ_PREC_F32, or AZ_PREC_BF16X3 / AZ_PREC_FP16 on 15x15 with channels %% 64 == 0");
-}
-
 // Every rand-wire create path: the precision, then the shapes the node kernels assume
 // (k_se_residual: C % 16 == 0 for its float4 channel quads, C <= 1024 and R = C / 16 <= 64 for
 // its fixed LDS arrays; no conv bias; the reference's adaptive pool to min(8, board)).
 static int check_rw_desc(const az_net_desc& d) {
-    if (int r = check_rw_precision(d, d.precision)) return r;
+    if (int r = check_precision(d, true, d.precision)) return r;
     if (d.conv_bias) return az_fail(AZ_ERR_ARG, "rand-wire convolutions carry no bias (conv_bias = 0)");
     if (d.channels < 16 || d.channels % 16 || d.channels > 1024)
         return az_fail(AZ_ERR_ARG, "rand-wire channels: a multiple of 16 in [16, 1024]");
@@ -775,8 +672,7 @@ void az_net_destroy(az_net* n) {
 
 int az_net_set_precision(az_net* n, int precision) {
     if (!n) return az_fail(AZ_ERR_ARG, "null net");
-    if (n->rw && check_rw_precision(n->d, precision)) return AZ_ERR_ARG;
-    if (int r = check_precision(n->d, precision)) return r;
+    if (int r = check_precision(n->d, n->rw, precision)) return r;
     n->d.precision = precision;
     return 0;
 }
@@ -784,37 +680,37 @@ int az_net_set_precision(az_net* n, int precision) {
 int az_net_trunk_kernel(az_net* n, char* name, int len) {
     if (!n || !name || len < 1) return az_fail(AZ_ERR_ARG, "null net / name");
     const az_net_desc& d = n->d;
-    const int prec = d.precision, F = d.channels, H = d.board_size;
-    const bool bf = (prec == AZ_PREC_BF16X3 || prec == AZ_PREC_F16X3 || prec == AZ_PREC_BF16 || prec == AZ_PREC_FP16) &&
-                    F % 32 == 0;
+    const int prec = d.precision;
     const bool f16 = prec == AZ_PREC_FP16;
-    if (n->rw) {
-        const bool v4x3 = prec == AZ_PREC_BF16X3 && d.max_batch >= 128;   // as rw_trunk dispatches
-        snprintf(name, len, f16 ? "conv3x3_v4<2, 128, 1>" : v4x3 ? "conv3x3_v4<0, 128, 0>" : "gemm_f32");
-        return 0;
+    const char* res = d.residual ? "true" : "false";
+    const NetPlan pl = plan_of(n);
+    if (!n->rw && d.blocks < 1) { snprintf(name, len, "gemm_f32"); return 0; }   // no trunk convs
+    if (pl.no_forward) return az_fail(AZ_ERR_ARG, "AZ_PREC_F16X3: no fp16-piece trunk for this net");
+    // the trunk's convs as net_forward builds them at the net's capacity
+    ConvBf16Args a = conv_args(n, d.max_batch, nullptr, d.channels);
+    a.pt = prec == AZ_PREC_F16X3 ? 2 : 1;
+    int r = 0;
+    switch (pl.trunk) {
+        case NET_TRUNK_RW_V4_FP16: snprintf(name, len, "conv3x3_v4<2, 128, 1>"); break;
+        case NET_TRUNK_RW_V4_X3: snprintf(name, len, "conv3x3_v4<0, 128, 0>"); break;
+        case NET_TRUNK_SMALL:   // as rocprofv3 names them
+            if (f16) snprintf(name, len, "k_smallnet_g<%d, 8, %s>", d.board_size, res);
+            else snprintf(name, len, "k_smallnet_x3<%d, 8, %s, %d>", d.board_size, res, a.pt);
+            break;
+        case NET_TRUNK_G8X3: r = az_conv_x3_name(a, name, len); break;
+        case NET_TRUNK_G8: r = az_conv_g8_name(a, f16 ? 2 : 1, name, len); break;
+        case NET_TRUNK_NHWC16: r = az_conv_bf16_name(a, f16 ? 2 : prec == AZ_PREC_BF16X3 ? 0 : 1, name, len); break;
+        default: snprintf(name, len, "gemm_f32"); break;
     }
-    if (!bf || d.blocks < 1) { snprintf(name, len, "gemm_f32"); return 0; }
-    if ((f16 || prec == AZ_PREC_BF16X3 || prec == AZ_PREC_F16X3) && az_smallnet_supported(H, F, n->cin_pad, d.pool, d.head_channels) &&
-        d.blocks <= az_smallnet_max_blocks()) {
-        if (f16) snprintf(name, len, "k_smallnet_g<%d, 8, %s>", H, d.residual ? "true" : "false");   // as rocprofv3 names it
-        else snprintf(name, len, "k_smallnet_x3<%d, 8, %s, %d>", H, d.residual ? "true" : "false", prec == AZ_PREC_F16X3 ? 2 : 1);
-        return 0;
-    }
-    // the trunk's second conv of a block, as net_forward builds it at the net's capacity
-    ConvBf16Args a{};
-    a.M = d.max_batch * n->HW; a.N = F; a.C = F; a.H = H; a.W = H; a.rows_per_sample = n->HW; a.relu = 1;
-    a.a_tail = n->act_elems * 2;
-    if (x3_trunk(n)) {
-        Layer probe;
-        probe.Wbk_bf = probe.Wbk_lo = probe.Wbk_fh = probe.Wbk_fl = n->zero;
-        probe.sx = reinterpret_cast<float*>(n->zero);
-        return az_conv_x3_name(x3_conv_args(n, probe, 1, 0, d.max_batch, nullptr), name, len) ? az_fail(AZ_ERR_ARG, "x3 name") : 0;
-    }
-    if (prec == AZ_PREC_F16X3) return az_fail(AZ_ERR_ARG, "AZ_PREC_F16X3: no fp16-piece trunk for this net");
-    const bool g8 = prec != AZ_PREC_BF16X3 && az_conv_g8_supported(H, H, F, F);
-    const int r = g8 ? az_conv_g8_name(a, f16 ? 2 : 1, name, len)
-                     : az_conv_bf16_name(a, f16 ? 2 : prec == AZ_PREC_BF16X3 ? 0 : 1, name, len);
     return r ? az_fail(AZ_ERR_ARG, "no trunk kernel for this net") : 0;
+}
+
+// Diagnostic: the net's plan (net_plan.h) as one line, e.g. "in=g8/in32 trunk=g8 tail=fused heads=x3-bf16".
+int az_diag_net_plan(az_net* n, char* out, int len) {
+    if (!n || !out || len < 1) return az_fail(AZ_ERR_ARG, "null net / buffer");
+    HIPCHK(hipSetDevice(n->e->device));
+    net_plan_line(plan_of(n), out, len);
+    return 0;
 }
 
 int az_net_profile(az_net* n, int enable) {

@@ -106,16 +106,15 @@ int load_heads(az_net* n, ParamCursor& pc);
 int net_load(az_net* n, const float* blob) {
     const az_net_desc& d = n->d;
     ParamCursor pc{blob};
-    const int F = d.channels, HC = d.head_channels, PP = d.pool * d.pool;
+    const int F = d.channels;
     std::vector<float> W, b;
-    const bool split = F % 32 == 0;
+    const NetPacks pk = net_packs(net_shape(d, false));
     // k_smallnet weights: every 3x3 layer as [tap][n][c] over 64 channels (input conv zero-padded):
     // fp16 for k_smallnet_g, bf16 hi / lo parts for k_smallnet_x3 (AZ_PREC_BF16X3), scaled fp16 hi / lo
     // pieces for k_smallnet_x3<.., 2> (AZ_PREC_F16X3).  Decided by the shape alone, like every other
     // piece set: az_net_set_precision only switches the dispatch, so a load packs what any precision the
     // shape accepts will read, and the buffer list recorded at the first load (net_weight_buffers) is
     // the same whatever precision the net had then
-    const bool sm = az_smallnet_supported(d.board_size, F, n->cin_pad, d.pool, HC) && d.blocks <= az_smallnet_max_blocks();
     // every layer's pieces (fp16, bf16 hi / lo, scaled fp16 hi / lo) are made from its [n][tap][c] rows, then
     // gathered to [tap][n][c]
     std::vector<uint16_t> smw, smh, sml, sfh, sfl;
@@ -134,21 +133,20 @@ int net_load(az_net* n, const float* blob) {
         ssx.insert(ssx.end(), sx.begin(), sx.end());
     };
     fold_conv(pc, F, d.in_planes, 3, n->cin_pad, d.conv_bias, W, b);
-    if (int r = upload_layer(n->in, W, b, F, 9 * n->cin_pad, 9, n->cin_pad, F % 32 == 0)) return r;  // 16-bit copies: g8 input conv
-    if (n->cin_pad == 16 && d.board_size != 15 && az_conv_g8_supported(d.board_size, d.board_size, F, F) &&
-        az_conv_g8_supported(d.board_size, d.board_size, 32, F)) {
+    if (int r = upload_layer(n->in, W, b, F, 9 * n->cin_pad, 9, n->cin_pad, pk.in16)) return r;  // 16-bit copies: g8 input conv
+    if (pk.in32) {
         std::vector<float> W32((size_t)F * 9 * 32, 0.0f);   // [F][9][32]: channels 16..31 zero
         for (size_t ot = 0; ot < (size_t)F * 9; ++ot) std::copy(&W[ot * 16], &W[ot * 16] + 16, &W32[ot * 32]);
         if (int r = upload_layer(n->in32, W32, b, F, 9 * 32, 9, 32, true)) return r;
     }
-    if (sm) sm_add(W, b, n->cin_pad);
+    if (pk.sm) sm_add(W, b, n->cin_pad);
     n->blk.resize(2 * d.blocks);
     for (int i = 0; i < 2 * d.blocks; ++i) {
         fold_conv(pc, F, F, 3, F, d.conv_bias, W, b);
-        if (int r = upload_layer(n->blk[i], W, b, F, 9 * F, 9, F, split)) return r;
-        if (sm) sm_add(W, b, F);
+        if (int r = upload_layer(n->blk[i], W, b, F, 9 * F, 9, F, pk.trunk16)) return r;
+        if (pk.sm) sm_add(W, b, F);
     }
-    if (sm) {
+    if (pk.sm) {
         const size_t ne = smw.size();
         if (!n->sm_W) {
             DALLOC(n->sm_W, ne); DALLOC(n->sm_Wf, ne); DALLOC(n->sm_Wxh, ne); DALLOC(n->sm_Wxl, ne); DALLOC(n->sm_b, smb.size());
@@ -227,8 +225,9 @@ int net_load_rw(az_net* n, const float* blob) {
     const int F = d.channels, R = F / 16;
     ParamCursor pc{blob};
     std::vector<float> W, b;
+    const NetPacks pk = net_packs(net_shape(d, true));
     fold_conv(pc, F, d.in_planes, 3, n->cin_pad, false, W, b);
-    if (int r = upload_layer(n->in, W, b, F, 9 * n->cin_pad, 9, n->cin_pad, false)) return r;
+    if (int r = upload_layer(n->in, W, b, F, 9 * n->cin_pad, 9, n->cin_pad, pk.in16)) return r;
     auto raw = [&](float** dst, size_t cnt) -> int {
         if (!*dst) DALLOC(*dst, cnt);
         HIPCHK(hipMemcpy(*dst, pc.take(cnt), cnt * 4, hipMemcpyHostToDevice));
@@ -244,7 +243,7 @@ int net_load_rw(az_net* n, const float* blob) {
         }
         for (int v : pl.order) {
             RwNode& nd = blk.node[v];
-            const bool h16 = F % 32 == 0;   // 16-bit weight copies: the fp16 node convs (conv3x3_v4)
+            const bool h16 = pk.trunk16;    // 16-bit weight copies: the node convs on conv3x3_v4
             fold_conv(pc, F, F, 3, F, false, W, b);
             if (int r = upload_layer(nd.c1, W, b, F, 9 * F, 9, F, h16)) return r;
             fold_conv(pc, F, F, 3, F, false, W, b);

@@ -1163,11 +1163,8 @@ __global__ __launch_bounds__(64 * NW, 1) void k_smallnet_x3(SmallNetArgs p) {
     smallnet_tail<HB, NW>(p, lds, OS, xr, wpre, b, tid, wp, l16, lg, J0);
 }
 
-bool az_smallnet_supported(int H, int C, int cin_pad, int pool, int head_channels) {
-    return H == 15 && C == SF && cin_pad == 16 && pool >= 1 && pool <= 8 && 2 * head_channels == SF && head_channels % 4 == 0;
-}
-// layers (2 * blocks + 1) whose biases fit the kernel's LDS
-int az_smallnet_max_blocks() { return (SmGeom<15>::MAXL - 1) / 2; }
+// az_smallnet_supported (net_plan.h): the filters, and the layers (2 * blocks + 1) whose biases fit the kernel's LDS
+static_assert(AZ_SMALLNET_F == SF && AZ_SMALLNET_MAX_BLOCKS == (SmGeom<15>::MAXL - 1) / 2, "net_plan.h: k_smallnet's limits");
 
 int az_smallnet_launch(const SmallNetArgs& a, int B, hipStream_t st) {
     if (!az_smallnet_supported(a.H, SF, 16, a.P, a.HC)) return -1;

@@ -141,6 +141,10 @@ int az_net_profile_read(az_net* n, double* trunk_ms, int64_t* trunk_launches, in
 /* The name of the HIP kernel the 3x3 trunk convs of this net dispatch at its max_batch
  * (measurement label, e.g. "conv3x3_v7<2, 15, SLIM>"; "gemm_f32" for the f32 path). */
 int az_net_trunk_kernel(az_net* n, char* name, int len);
+/* Diagnostic: how this net runs at its current precision, as one line -- input stage, trunk kernel
+ * family, tail and head FC variant, e.g. "in=g8/in32 trunk=g8 tail=fused heads=x3-bf16" (the route
+ * table of DESIGN.md).  Needs neither a load nor a forward. */
+int az_diag_net_plan(az_net* n, char* out, int len);
 /* predictBatch semantics: policy = softmax over A (max-subtracted, sequential fp32 sum,
  * torch_neural_network.cpp:296-316), value [B]. */
 int az_net_predict_batch(az_net* n, const float* planes, int B, float* policy, float* value);
