@@ -91,6 +91,8 @@ EXPORTS = {
     "az_net_profile_read": (c_int, [vp, P(ctypes.c_double), P(c_int64), P(c_int64)]),
     "az_net_trunk_kernel": (c_int, [vp, ctypes.c_char_p, c_int]),
     "az_diag_net_plan": (c_int, [vp, ctypes.c_char_p, c_int]),
+    "az_diag_device_mem": (c_int, [P(c_int64), P(c_int64)]),
+    "az_diag_fail_alloc": (c_int, [c_int]),
     "az_search_create": (c_int, [vp, vp, P(SearchCfg), P(vp)]),
     "az_search_destroy": (None, [vp]),
     "az_search_new_games": (c_int, [vp, P(c_int), c_int]),

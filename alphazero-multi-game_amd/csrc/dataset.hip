@@ -18,13 +18,21 @@
 #include "engine_internal.h"
 #include "tree_kernels.h"
 
+// Example rows of one storage set, in a pool of their own: assigning or dropping a Rows frees them.
+struct Rows {
+    float* states = nullptr; float* policy = nullptr; int* plen = nullptr; float* value = nullptr;
+    int64_t cap = 0;
+    DevPool mem;
+};
+
 struct az_dataset {
     az_engine* e = nullptr;
     int game = 0, bs = 0, A = 0, NA = 0, C = 0;
-    int64_t E = 0, cap = 0;
-    float* states = nullptr; float* policy = nullptr; int* plen = nullptr; float* value = nullptr;
+    int64_t E = 0;
+    Rows rows;
     uint64_t* zzero = nullptr;             // Go capture code updates a hash: zero keys (planes need none)
-    std::vector<void*> scratch;            // per-call uploads
+    DevPool misc;                          // zzero
+    DevPool scratch;                       // per-call uploads
     hipEvent_t ev0 = nullptr, ev1 = nullptr;
     double last_ms = 0.0, last_bytes = 0.0;
     std::mt19937 rng{std::random_device{}()};   // Dataset::rng_ (dataset.cpp:57)
@@ -33,53 +41,30 @@ struct az_dataset {
 
 namespace {
 
-// Example rows of one storage set.
-struct Rows {
-    float* states = nullptr; float* policy = nullptr; int* plen = nullptr; float* value = nullptr;
-    int64_t cap = 0;
-    void release() {
-        for (void* p : {(void*)states, (void*)policy, (void*)plen, (void*)value}) if (p) (void)hipFree(p);
-        *this = Rows{};
-    }
-};
-
 int rows_alloc(Rows& r, int64_t n, int C, int A, int NA) {
-    DALLOC(r.states, (size_t)n * C * A);
-    DALLOC(r.policy, (size_t)n * NA);
-    DALLOC(r.plen, (size_t)n);
-    DALLOC(r.value, (size_t)n);
+    if (int rc = r.mem.alloc(&r.states, (size_t)n * C * A)) return rc;
+    if (int rc = r.mem.alloc(&r.policy, (size_t)n * NA)) return rc;
+    if (int rc = r.mem.alloc(&r.plen, (size_t)n)) return rc;
+    if (int rc = r.mem.alloc(&r.value, (size_t)n)) return rc;
     r.cap = n;
     return 0;
 }
 
-Rows rows_of(az_dataset* d) { Rows r; r.states = d->states; r.policy = d->policy; r.plen = d->plen; r.value = d->value; r.cap = d->cap; return r; }
-void set_rows(az_dataset* d, const Rows& r) { d->states = r.states; d->policy = r.policy; d->plen = r.plen; d->value = r.value; d->cap = r.cap; }
-
-void free_scratch(az_dataset* d) {
-    for (void* p : d->scratch) (void)hipFree(p);
-    d->scratch.clear();
-}
-
 template <class T>
 int upload(az_dataset* d, const T* host, size_t n, T** dev) {
-    int r = dalloc(dev, n);
+    int r = d->scratch.alloc(dev, n);
     if (r) return r;
-    d->scratch.push_back(*dev);
     if (n && host) HIPCHK(hipMemcpyAsync(*dev, host, n * sizeof(T), hipMemcpyHostToDevice, d->e->stream));
     return 0;
 }
 
 // storage for n rows (grow-only; contents are not preserved)
 int reserve(az_dataset* d, int64_t n) {
-    if (n <= d->cap) return 0;
-    Rows r = rows_of(d);
-    r.release();
-    set_rows(d, r);
-    Rows nr;
-    int rc = rows_alloc(nr, n, d->C, d->A, d->NA);
-    if (rc) { nr.release(); return rc; }
-    set_rows(d, nr);
-    return 0;
+    if (n <= d->rows.cap) return 0;
+    d->rows = Rows{};
+    int rc = rows_alloc(d->rows, n, d->C, d->A, d->NA);
+    if (rc) d->rows = Rows{};
+    return rc;
 }
 
 int check_perm(const int64_t* order, int64_t n) {
@@ -97,8 +82,8 @@ int gather_rows(az_dataset* d, const long long* idx_dev, int64_t n, Rows& out) {
     const int row = d->C * d->A;
     for (int64_t b = 0; b < n; b += 1 << 30) {
         const int cnt = (int)std::min<int64_t>(n - b, 1 << 30);
-        hipLaunchKernelGGL(k_dataset_gather, dim3(cnt), dim3(256), 0, d->e->stream, d->states, d->policy, d->plen,
-                           d->value, row, d->NA, idx_dev + b, cnt, out.states + b * row, out.policy + b * d->NA,
+        hipLaunchKernelGGL(k_dataset_gather, dim3(cnt), dim3(256), 0, d->e->stream, d->rows.states, d->rows.policy, d->rows.plen,
+                           d->rows.value, row, d->NA, idx_dev + b, cnt, out.states + b * row, out.policy + b * d->NA,
                            out.plen + b, out.value + b);
     }
     HIPCHK(hipGetLastError());
@@ -123,7 +108,7 @@ int az_dataset_create(az_engine* e, int game_type, int board_size, az_dataset** 
     d->A = board_size * board_size;
     d->NA = d->game == GAME_GO ? d->A + 1 : d->A;
     d->C = d->game == GAME_GO ? 8 : 11;
-    int r = dalloc(&d->zzero, (size_t)2 * d->A);
+    int r = d->misc.alloc(&d->zzero, (size_t)2 * d->A);
     hipError_t he = hipSuccess;
     if (!r) he = hipMemset(d->zzero, 0, (size_t)2 * d->A * 8);
     if (!r && he == hipSuccess) he = hipEventCreate(&d->ev0);
@@ -137,10 +122,6 @@ int az_dataset_create(az_engine* e, int game_type, int board_size, az_dataset** 
 void az_dataset_destroy(az_dataset* d) {
     if (!d) return;
     (void)hipSetDevice(d->e->device);
-    free_scratch(d);
-    Rows r = rows_of(d);
-    r.release();
-    if (d->zzero) (void)hipFree(d->zzero);
     if (d->ev0) (void)hipEventDestroy(d->ev0);
     if (d->ev1) (void)hipEventDestroy(d->ev1);
     delete d;
@@ -203,12 +184,12 @@ int az_dataset_extract(az_dataset* d, int n_games, const int* n_moves, const int
     if (!r) r = upload(d, policies, (size_t)pol_off[(size_t)M], &pp);
     if (!r) r = upload(d, results, (size_t)n_games, &rs);
     if (!r && order) r = upload(d, dst.data(), dst.size(), &ds);
-    if (r) { (void)hipStreamSynchronize(d->e->stream); free_scratch(d); return r; }
+    if (r) { (void)hipStreamSynchronize(d->e->stream); d->scratch.clear(); return r; }
     DatasetDev dv{};
     dv.game = d->game; dv.bs = d->bs; dv.A = d->A; dv.NA = d->NA; dv.C = d->C; dv.K = K; dv.n_games = n_games;
     dv.move_off = mo; dv.actions = ac; dv.pol_off = po; dv.n_children = nc; dv.policies = pp; dv.results = rs;
     dv.dst = ds;
-    dv.states = d->states; dv.policy = d->policy; dv.plen = d->plen; dv.value = d->value;
+    dv.states = d->rows.states; dv.policy = d->rows.policy; dv.plen = d->rows.plen; dv.value = d->rows.value;
     TreeDev t{};
     t.bs = d->bs; t.A = d->A; t.NA = d->NA; t.game = d->game; t.zpiece = d->zzero;
     hipError_t he = hipEventRecord(d->ev0, d->e->stream);
@@ -218,7 +199,7 @@ int az_dataset_extract(az_dataset* d, int n_games, const int* n_moves, const int
     }
     if (he == hipSuccess) he = hipEventRecord(d->ev1, d->e->stream);
     hipError_t se = hipStreamSynchronize(d->e->stream);
-    free_scratch(d);
+    d->scratch.clear();
     if (he == hipSuccess) he = se;
     if (he != hipSuccess) return az_fail(AZ_ERR_HIP, "k_dataset_extract: %s", hipGetErrorString(he));
     float ms = 0.0f;
@@ -270,10 +251,10 @@ int az_dataset_upload(az_dataset* d, int64_t n, const float* states, const float
     d->E = n;
     if (n == 0) return 0;
     const size_t row = (size_t)d->C * d->A;
-    HIPCHK(hipMemcpy(d->states, states, (size_t)n * row * 4, hipMemcpyHostToDevice));
-    HIPCHK(hipMemcpy(d->policy, policy, (size_t)n * d->NA * 4, hipMemcpyHostToDevice));
-    HIPCHK(hipMemcpy(d->plen, policy_len, (size_t)n * 4, hipMemcpyHostToDevice));
-    HIPCHK(hipMemcpy(d->value, value, (size_t)n * 4, hipMemcpyHostToDevice));
+    HIPCHK(hipMemcpy(d->rows.states, states, (size_t)n * row * 4, hipMemcpyHostToDevice));
+    HIPCHK(hipMemcpy(d->rows.policy, policy, (size_t)n * d->NA * 4, hipMemcpyHostToDevice));
+    HIPCHK(hipMemcpy(d->rows.plen, policy_len, (size_t)n * 4, hipMemcpyHostToDevice));
+    HIPCHK(hipMemcpy(d->rows.value, value, (size_t)n * 4, hipMemcpyHostToDevice));
     return 0;
 }
 
@@ -291,12 +272,10 @@ int az_dataset_permute(az_dataset* d, const int64_t* order) {
     if (!r) r = upload(d, (const long long*)order, (size_t)d->E, &idx);
     if (!r) r = gather_rows(d, idx, d->E, nr);
     hipError_t se = hipStreamSynchronize(d->e->stream);
-    free_scratch(d);
+    d->scratch.clear();
     if (!r && se != hipSuccess) r = az_fail(AZ_ERR_HIP, "dataset permute: %s", hipGetErrorString(se));
-    if (r) { nr.release(); return r; }
-    Rows old = rows_of(d);
-    old.release();
-    set_rows(d, nr);
+    if (r) return r;
+    d->rows = std::move(nr);
     return 0;
 }
 
@@ -325,8 +304,7 @@ int az_dataset_gather(az_dataset* d, const int64_t* idx, int n, float* states, f
     hipError_t se = hipStreamSynchronize(d->e->stream);
     if (he == hipSuccess) he = se;
     if (!r && he != hipSuccess) r = az_fail(AZ_ERR_HIP, "dataset gather: %s", hipGetErrorString(he));
-    free_scratch(d);
-    t.release();
+    d->scratch.clear();
     return r;
 }
 

@@ -33,6 +33,7 @@ struct az_dist {
     double* dbuf = nullptr;           // counters staging [AZ_DIST_MAX_COUNTERS]
     float* blob = nullptr;            // canonical weight blob staging
     size_t blob_cap = 0;
+    DevPool pool;                     // dbuf and blob
     std::mutex mu;
 };
 
@@ -108,12 +109,12 @@ int az_dist_init(az_engine* e, int rank, int world, const unsigned char* id, int
     if (!e || !id || !out || world < 1 || rank < 0 || rank >= world) return az_fail(AZ_ERR_ARG, "bad argument");
     *out = nullptr;
     HIPCHK(hipSetDevice(e->device));
-    auto* d = new az_dist();
+    std::unique_ptr<az_dist, void (*)(az_dist*)> d(new az_dist(), az_dist_destroy);   // every early return frees it
     d->e = e;
     d->rank = rank;
     d->world = world;
     if (timeout_ms > 0) d->timeout_ms = timeout_ms;
-    if (int r = dalloc(&d->dbuf, AZ_DIST_MAX_COUNTERS)) { delete d; return r; }
+    if (int r = d->pool.alloc(&d->dbuf, AZ_DIST_MAX_COUNTERS)) return r;
     ncclUniqueId u;
     std::memcpy(&u, id, AZ_DIST_ID_BYTES);
     // ncclCommInitRank blocks until every rank joined: it runs on a helper thread, awaited with the
@@ -133,20 +134,13 @@ int az_dist_init(az_engine* e, int rank, int world, const unsigned char* id, int
     }).detach();
     const auto t0 = std::chrono::steady_clock::now();
     while (!job->done) {
-        if (std::chrono::steady_clock::now() - t0 > std::chrono::milliseconds(d->timeout_ms)) {
-            (void)hipFree(d->dbuf);
-            delete d;
+        if (std::chrono::steady_clock::now() - t0 > std::chrono::milliseconds(d->timeout_ms))
             return az_fail(AZ_ERR_STATE, "ncclCommInitRank: not every rank joined within %d ms", timeout_ms > 0 ? timeout_ms : 600000);
-        }
         std::this_thread::sleep_for(std::chrono::milliseconds(1));
     }
-    if (job->r != ncclSuccess) {
-        (void)hipFree(d->dbuf);
-        delete d;
-        return nccl_fail(job->r, "ncclCommInitRank");
-    }
+    if (job->r != ncclSuccess) return nccl_fail(job->r, "ncclCommInitRank");
     d->comm = job->comm;
-    *out = d;
+    *out = d.release();
     return 0;
 }
 
@@ -157,8 +151,6 @@ void az_dist_destroy(az_dist* d) {
         if (hipStreamSynchronize(d->e->stream) == hipSuccess) ncclCommDestroy(d->comm);
         else ncclCommAbort(d->comm);
     }
-    if (d->dbuf) (void)hipFree(d->dbuf);
-    if (d->blob) (void)hipFree(d->blob);
     delete d;
 }
 
@@ -199,11 +191,11 @@ int az_net_broadcast_weights(az_dist* d, az_net* n, int root) {
     hipStream_t st = d->e->stream;
     const size_t np = net_param_count(n);
     if (d->rank == root && net_host_blob(n).size() != np) return az_fail(AZ_ERR_STATE, "root net has no weights loaded");
-    std::vector<std::pair<void*, size_t>> bufs;
+    std::vector<DevPool::Buf> bufs;
     if (int r = net_weight_buffers(n, bufs)) return r;
     // every rank must hold the same layout: (buffer count, total bytes, parameters) min == max
     double shape[3] = {(double)bufs.size(), 0.0, (double)np};
-    for (auto& b : bufs) shape[1] += (double)b.second;
+    for (auto& b : bufs) shape[1] += (double)b.bytes;
     double lo[3], hi[3];
     const double neg[3] = {-shape[0], -shape[1], -shape[2]};
     if (int r = allreduce_host(d, shape, hi, 3, ncclMax, "az_net_broadcast_weights")) return r;
@@ -212,10 +204,9 @@ int az_net_broadcast_weights(az_dist* d, az_net* n, int root) {
         if (hi[i] != -lo[i])
             return az_fail(AZ_ERR_ARG, "az_net_broadcast_weights: the ranks' nets differ (buffers / bytes / parameters)");
     if (d->blob_cap < np) {
-        if (d->blob) (void)hipFree(d->blob);
-        d->blob = nullptr;
+        d->pool.release(d->blob);
         d->blob_cap = 0;
-        if (int r = dalloc(&d->blob, np)) return r;
+        if (int r = d->pool.alloc(&d->blob, np)) return r;
         d->blob_cap = np;
     }
     if (d->rank == root) HIPCHK(hipMemcpyAsync(d->blob, net_host_blob(n).data(), np * 4, hipMemcpyHostToDevice, st));
@@ -227,7 +218,7 @@ int az_net_broadcast_weights(az_dist* d, az_net* n, int root) {
         NCCLCHK(ncclGroupStart());
         ncclResult_t gr = ncclSuccess;
         for (size_t i = g0; gr == ncclSuccess && i < std::min(bufs.size(), g0 + GROUP); ++i)
-            gr = ncclBroadcast(bufs[i].first, bufs[i].first, bufs[i].second, ncclUint8, root, d->comm, st);
+            gr = ncclBroadcast(bufs[i].p, bufs[i].p, bufs[i].bytes, ncclUint8, root, d->comm, st);
         const ncclResult_t ge = ncclGroupEnd();
         if (gr != ncclSuccess) return nccl_fail(gr, "ncclBroadcast");
         if (ge != ncclSuccess) return nccl_fail(ge, "ncclGroupEnd");
@@ -252,14 +243,14 @@ int az_diag_net_copy_weights(az_net* dst, az_net* src) {
     std::lock_guard<std::mutex> lb(net_mutex(src));
     HIPCHK(hipSetDevice(net_engine(src)->device));
     if (net_host_blob(src).size() != net_param_count(src)) return az_fail(AZ_ERR_STATE, "src has no weights loaded");
-    std::vector<std::pair<void*, size_t>> a, b;
+    std::vector<DevPool::Buf> a, b;
     if (int r = net_weight_buffers(dst, a)) return r;
     if (int r = net_weight_buffers(src, b)) return r;
     if (a.size() != b.size() || net_param_count(dst) != net_param_count(src))
         return az_fail(AZ_ERR_ARG, "the nets differ");
     for (size_t i = 0; i < a.size(); ++i) {
-        if (a[i].second != b[i].second) return az_fail(AZ_ERR_ARG, "the nets differ (buffer %zu)", i);
-        HIPCHK(hipMemcpy(a[i].first, b[i].first, a[i].second, hipMemcpyDeviceToDevice));
+        if (a[i].bytes != b[i].bytes) return az_fail(AZ_ERR_ARG, "the nets differ (buffer %zu)", i);
+        HIPCHK(hipMemcpy(a[i].p, b[i].p, a[i].bytes, hipMemcpyDeviceToDevice));
     }
     // device-to-device copies on the null stream need not be done when hipMemcpy returns, and the forwards
     // run on the engine's non-blocking stream, which does not wait for them (as az_net_load_weights)

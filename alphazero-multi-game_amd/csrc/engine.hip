@@ -70,4 +70,12 @@ int az_engine_device_name(az_engine* e, char* buf, int len) {
 
 int az_diag_set_step_trace(int on) { g_step_trace = on; return 0; }
 
+int az_diag_device_mem(int64_t* bytes, int64_t* buffers) {
+    if (bytes) *bytes = DevPool::live_bytes.load();
+    if (buffers) *buffers = DevPool::live_bufs.load();
+    return 0;
+}
+
+int az_diag_fail_alloc(int nth) { return DevPool::fail_in.exchange(nth < 0 ? -1 : nth); }
+
 }  // extern "C"

@@ -15,6 +15,7 @@
 #include <vector>
 
 #include "../../include/az_engine.h"
+#include "dev_pool.h"
 
 struct az_engine {
     int device = 0;
@@ -23,38 +24,17 @@ struct az_engine {
     std::mutex mu;
 };
 
-// Sets the az_last_error() message; returns code.
-int az_fail(int code, const char* fmt, ...) __attribute__((format(printf, 2, 3)));
-
 #define HIPCHK(x)                                                                            \
     do {                                                                                     \
         hipError_t e_ = (x);                                                                 \
         if (e_ != hipSuccess) return az_fail(AZ_ERR_HIP, "%s: %s (%s:%d)", #x, hipGetErrorString(e_), __FILE__, __LINE__); \
     } while (0)
 
-// While set (a net's first weight load, WeightRegistry), every dalloc is recorded here: the list of
-// device buffers that hold a net's weights, in allocation order (az_net_broadcast_weights).
-inline thread_local std::vector<std::pair<void*, size_t>>* g_dalloc_reg = nullptr;
-struct WeightRegistry {
-    explicit WeightRegistry(std::vector<std::pair<void*, size_t>>* r) { g_dalloc_reg = r; }
-    ~WeightRegistry() { g_dalloc_reg = nullptr; }
-};
-
-template <class T>
-inline int dalloc(T** p, size_t n) {
-    if (n == 0) n = 1;
-    hipError_t e = hipMalloc((void**)p, n * sizeof(T));
-    if (e != hipSuccess) return az_fail(AZ_ERR_OOM, "hipMalloc(%zu bytes): %s", n * sizeof(T), hipGetErrorString(e));
-    if (g_dalloc_reg) g_dalloc_reg->emplace_back((void*)*p, n * sizeof(T));
-    return 0;
-}
-#define DALLOC(p, n) do { int r_ = dalloc(&(p), (n)); if (r_) return r_; } while (0)
-
 // Net internals for the multi-GPU collectives (dist.hip, az_net_broadcast_weights):
 // the device buffers of the net's loaded weights (every packed piece set), allocating them with a
 // load of zero weights if the net was never loaded; the canonical blob on the host.
 struct az_net;
-int net_weight_buffers(az_net* n, std::vector<std::pair<void*, size_t>>& out);
+int net_weight_buffers(az_net* n, std::vector<DevPool::Buf>& out);
 const std::vector<float>& net_host_blob(az_net* n);
 size_t net_param_count(az_net* n);
 az_engine* net_engine(az_net* n);
@@ -83,7 +63,11 @@ struct ProfClock {
         for (size_t i = 0; i < used; ++i) out[i] = (double)h[i] * 1e-5;
         return out;
     }
-    void release() { if (d) (void)hipFree(d); d = nullptr; used = 0; }
+    // profiling switched on: the stamp buffer, once, from the owning handle's pool
+    int enable(DevPool& pool) {
+        if (!d && pool.alloc(&d, CAP)) return az_fail(AZ_ERR_OOM, "profile clock buffer");
+        return 0;
+    }
 };
 
 // Profiling stamps (ProfClock) are recorded on one simulation step / forward in AZ_PROF_EVERY

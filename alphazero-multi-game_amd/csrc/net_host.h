@@ -84,12 +84,12 @@ struct az_net {
     float* rw_ws = nullptr;           // their split-K partials [rw_splits][rows][F]
     bool loaded = false;
     std::vector<float> host_blob;   // canonical blob of the loaded weights (az_net_get_weights)
-    // the device buffers of the loaded weights, in allocation order (recorded at the first load;
-    // later loads rewrite the same buffers): what az_net_broadcast_weights sends
-    std::vector<std::pair<void*, size_t>> wbufs;
-    // every activation / workspace buffer (pointer, bytes before any zeroed tail): the poison
-    // diagnostic (az_diag_set_poison) overwrites them before each forward
-    std::vector<std::pair<void*, size_t>> scratch;
+    // Device memory (dev_pool.h); the named pointers above and in the layers point into these.
+    // weights: every weight buffer, in the loader's order (a load allocates what is missing and
+    // rewrites the rest): what az_net_broadcast_weights sends.  acts: every activation / workspace
+    // buffer (bytes before any zeroed tail): the poison diagnostic (az_diag_set_poison) overwrites
+    // them before each forward.  misc: d_nb, ovf, zero, the router tables, the profile clock.
+    DevPool weights, acts, misc;
     // profiling: HIP events bracketing the 3x3 trunk of every forward (on the launch stream)
     bool prof = false;
     ProfClock pc;                 // sampled trunk timing (az_net_profile)

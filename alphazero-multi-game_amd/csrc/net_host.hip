@@ -138,9 +138,9 @@ float* trunk_rw(az_net* n, int trunk, int B, const int* nb, hipStream_t st) {
 int g_poison = -1;
 int poison_net(az_net* n, hipStream_t st, bool inputs) {
     if (g_poison < 0) return 0;
-    for (const auto& b : n->scratch) {
-        const bool in = b.first == (void*)n->x0 || b.first == (void*)n->in_nchw;
-        if (in == inputs) HIPCHK(hipMemsetAsync(b.first, g_poison, b.second, st));
+    for (const DevPool::Buf& b : n->acts.bufs) {
+        const bool in = b.p == (void*)n->x0 || b.p == (void*)n->in_nchw;
+        if (in == inputs) HIPCHK(hipMemsetAsync(b.p, g_poison, b.bytes, st));
     }
     return 0;
 }
@@ -449,16 +449,13 @@ static int net_create(az_engine* e, const az_net_desc* d, az_net** out, bool rw,
     const size_t B = d->max_batch, rows = B * n->HW, F = d->channels;
     n->act_elems = rows * F;
     int r = 0;
-    auto A_ = [&](float** p, size_t cnt) {
-        if (!r) r = dalloc(p, cnt);
-        if (!r) n->scratch.emplace_back((void*)*p, cnt * 4);
-    };
+    auto A_ = [&](float** p, size_t cnt) { if (!r) r = n->acts.alloc(p, cnt); };
     // 16-bit activation planes carry a zeroed tail (AZ_ACT_TAIL elements): the v6 conv points the
     // DMA of halo padding rows there
     auto H_ = [&](uint16_t** p, size_t cnt) {
-        if (!r) r = dalloc(p, cnt + AZ_ACT_TAIL);
+        if (r) return;
+        r = n->acts.alloc(p, cnt, AZ_ACT_TAIL);
         if (!r && hipMemset(*p + cnt, 0, AZ_ACT_TAIL * 2) != hipSuccess) r = az_fail(AZ_ERR_HIP, "hipMemset");
-        if (!r) n->scratch.emplace_back((void*)*p, cnt * 2);
     };
     A_(&n->x0, rows * n->cin_pad);
     A_(&n->h0, rows * F); A_(&n->h1, rows * F); A_(&n->t, rows * F);
@@ -496,7 +493,7 @@ static int net_create(az_engine* e, const az_net_desc* d, az_net** out, bool rw,
             if (r || ids.size() < 2) return;
             std::vector<const float*> t;
             for (int u : ids) t.push_back(n->rw_out[u]);
-            if (hipMalloc((void**)dst, t.size() * sizeof(float*)) != hipSuccess ||
+            if (n->misc.alloc(dst, t.size()) ||
                 hipMemcpy((void*)*dst, t.data(), t.size() * sizeof(float*), hipMemcpyHostToDevice) != hipSuccess)
                 r = az_fail(AZ_ERR_OOM, "router input table");
         };
@@ -505,10 +502,10 @@ static int net_create(az_engine* e, const az_net_desc* d, az_net** out, bool rw,
             table(blk.plan.outputs, &blk.outs);
         }
     }
-    if (!r) r = dalloc(&n->d_nb, 1);
-    if (!r) r = dalloc(&n->ovf, 1);
+    if (!r) r = n->misc.alloc(&n->d_nb, 1);
+    if (!r) r = n->misc.alloc(&n->ovf, 1);
     if (!r && hipMemset(n->ovf, 0, 4) != hipSuccess) r = az_fail(AZ_ERR_HIP, "memset");
-    if (!r) r = dalloc(&n->zero, 128);
+    if (!r) r = n->misc.alloc(&n->zero, 128);
     if (!r && hipMemset(n->zero, 0, 256) != hipSuccess) r = az_fail(AZ_ERR_HIP, "memset");
     // the memsets above run on the null stream, the forwards on the engine's non-blocking stream,
     // which does not wait for it: finish them here
@@ -645,29 +642,7 @@ int az_randwire_graph(int block, int* order, int* topo, int* inputs, int* n_inpu
 void az_net_destroy(az_net* n) {
     if (!n) return;
     (void)hipSetDevice(n->e->device);
-    auto F = [](void* p) { if (p) (void)hipFree(p); };
-    std::vector<Layer*> ls = {&n->in, &n->in32, &n->pconv, &n->vconv, &n->hconv, &n->pfc, &n->vfc1, &n->vfc2};
-    for (auto& l : n->blk) ls.push_back(&l);
-    for (auto& blk : n->rwb) {
-        ls.push_back(&blk.out_router);
-        F((void*)blk.outs);
-        for (auto& nd : blk.node) {
-            ls.push_back(&nd.router); ls.push_back(&nd.c1); ls.push_back(&nd.c2);
-            F(nd.w1); F(nd.b1); F(nd.w2); F(nd.b2); F((void*)nd.ins);
-        }
-    }
-    for (float* p : n->rw_out) F(p);
-    F(n->rw_t2); F(n->rw_in); F(n->rw_ws);
-    for (Layer* l : ls) { F(l->W); F(l->b); F(l->Whi); F(l->Wlo); F(l->Wh16); F(l->Wbk_bf); F(l->Wbk_h); F(l->Wbk_lo);
-                          F(l->Wbk_fh); F(l->Wbk_fl); F(l->bx); F(l->sx); }
-    for (void* p : {(void*)n->x0, (void*)n->h0, (void*)n->h1, (void*)n->t, (void*)n->pool, (void*)n->pp, (void*)n->vp, (void*)n->hpv,
-                    (void*)n->v1, (void*)n->ws, (void*)n->logits, (void*)n->value, (void*)n->soft, (void*)n->in_nchw, (void*)n->d_nb, (void*)n->ovf,
-                    (void*)n->hh[0], (void*)n->hh[1], (void*)n->hl[0], (void*)n->hl[1], (void*)n->th, (void*)n->tl,
-                    (void*)n->zero, (void*)n->sm_W, (void*)n->sm_Wf, (void*)n->sm_Wxh, (void*)n->sm_Wxl, (void*)n->sm_b, (void*)n->fcx_hi, (void*)n->fcx_lo, (void*)n->fcf_hi, (void*)n->fcf_lo, (void*)n->fcf_rs,
-                    (void*)n->sm_Wfh, (void*)n->sm_Wfl, (void*)n->sm_bx, (void*)n->sm_sx})
-        F(p);
-    n->pc.release();
-    delete n;
+    delete n;   // its pools free every device buffer
 }
 
 int az_net_set_precision(az_net* n, int precision) {
@@ -717,9 +692,9 @@ int az_net_profile(az_net* n, int enable) {
     if (!n) return az_fail(AZ_ERR_ARG, "null net");
     std::lock_guard<std::mutex> lk(n->mu);
     n->prof = enable != 0;
-    if (n->prof && !n->pc.d) {
+    if (n->prof) {
         HIPCHK(hipSetDevice(n->e->device));
-        if (hipMalloc((void**)&n->pc.d, ProfClock::CAP * 8) != hipSuccess) { n->pc.d = nullptr; return az_fail(AZ_ERR_OOM, "profile clock buffer"); }
+        if (int r = n->pc.enable(n->misc)) return r;
     }
     n->pc.used = 0; n->prof_launches = 0; n->prof_forwards = 0; n->prof_tick = 0; n->prof_sampled = 0;
     return 0;

@@ -64,31 +64,33 @@ std::vector<PSpec> rw_spec(const az_net_desc& d, const std::vector<RwBlock>& rwb
     return s;
 }
 
-int upload_layer(Layer& L, const std::vector<float>& W, const std::vector<float>& b, int N, int K, int taps, int C,
-                 bool split) {
+// A weight buffer of net n, allocated from n->weights where it is still missing: a load after one
+// that failed part-way allocates the rest, so the pool always ends up in the loader's order.
+#define WBUF(p, cnt) do { if (!(p)) { if (int r_ = n->weights.alloc(&(p), (cnt))) return r_; } } while (0)
+
+int upload_layer(az_net* n, Layer& L, const std::vector<float>& W, const std::vector<float>& b, int N, int K, int taps,
+                 int C, bool split) {
     L.N = N; L.K = K; L.Kpad = (K + 31) / 32 * 32; L.taps = taps; L.C = C;
-    if (!L.W) { DALLOC(L.W, W.size()); DALLOC(L.b, b.size()); }
+    WBUF(L.W, W.size()); WBUF(L.b, b.size());
     HIPCHK(hipMemcpy(L.W, W.data(), W.size() * 4, hipMemcpyHostToDevice));
     HIPCHK(hipMemcpy(L.b, b.data(), b.size() * 4, hipMemcpyHostToDevice));
     if (split) {
         std::vector<uint16_t> hi(W.size()), lo(W.size());
         split_bf16(W.data(), W.size(), hi.data(), lo.data());
-        if (!L.Whi) { DALLOC(L.Whi, W.size()); DALLOC(L.Wlo, W.size()); }
+        WBUF(L.Whi, W.size()); WBUF(L.Wlo, W.size());
         HIPCHK(hipMemcpy(L.Whi, hi.data(), hi.size() * 2, hipMemcpyHostToDevice));
         HIPCHK(hipMemcpy(L.Wlo, lo.data(), lo.size() * 2, hipMemcpyHostToDevice));
         std::vector<uint16_t> h16(W.size());
         to_f16(W.data(), W.size(), h16.data());
-        if (!L.Wh16) DALLOC(L.Wh16, W.size());
+        WBUF(L.Wh16, W.size());
         HIPCHK(hipMemcpy(L.Wh16, h16.data(), h16.size() * 2, hipMemcpyHostToDevice));
         if (taps == 9 && C % 16 == 0) {
             // chunk-blocked copies of every piece set (v5 / v6 / v7 convs); the fp16 pieces of AZ_PREC_F16X3
             std::vector<uint16_t> fh(W.size()), fl(W.size());
             std::vector<float> bx(N), sx(N);
             pow2_split_rows(W.data(), N, (size_t)9 * C, b.data(), fh.data(), fl.data(), bx.data(), sx.data());
-            if (!L.Wbk_bf) {
-                DALLOC(L.Wbk_bf, W.size()); DALLOC(L.Wbk_h, W.size()); DALLOC(L.Wbk_lo, W.size());
-                DALLOC(L.Wbk_fh, W.size()); DALLOC(L.Wbk_fl, W.size()); DALLOC(L.bx, N); DALLOC(L.sx, N);
-            }
+            WBUF(L.Wbk_bf, W.size()); WBUF(L.Wbk_h, W.size()); WBUF(L.Wbk_lo, W.size());
+            WBUF(L.Wbk_fh, W.size()); WBUF(L.Wbk_fl, W.size()); WBUF(L.bx, N); WBUF(L.sx, N);
             HIPCHK(hipMemcpy(L.Wbk_bf, chunk_blocked(hi, N, C).data(), W.size() * 2, hipMemcpyHostToDevice));
             HIPCHK(hipMemcpy(L.Wbk_h, chunk_blocked(h16, N, C).data(), W.size() * 2, hipMemcpyHostToDevice));
             HIPCHK(hipMemcpy(L.Wbk_lo, chunk_blocked(lo, N, C).data(), W.size() * 2, hipMemcpyHostToDevice));
@@ -113,8 +115,8 @@ int net_load(az_net* n, const float* blob) {
     // fp16 for k_smallnet_g, bf16 hi / lo parts for k_smallnet_x3 (AZ_PREC_BF16X3), scaled fp16 hi / lo
     // pieces for k_smallnet_x3<.., 2> (AZ_PREC_F16X3).  Decided by the shape alone, like every other
     // piece set: az_net_set_precision only switches the dispatch, so a load packs what any precision the
-    // shape accepts will read, and the buffer list recorded at the first load (net_weight_buffers) is
-    // the same whatever precision the net had then
+    // shape accepts will read, and the weight pool (net_weight_buffers) is the same whatever precision
+    // the net had at any load
     // every layer's pieces (fp16, bf16 hi / lo, scaled fp16 hi / lo) are made from its [n][tap][c] rows, then
     // gathered to [tap][n][c]
     std::vector<uint16_t> smw, smh, sml, sfh, sfl;
@@ -133,25 +135,23 @@ int net_load(az_net* n, const float* blob) {
         ssx.insert(ssx.end(), sx.begin(), sx.end());
     };
     fold_conv(pc, F, d.in_planes, 3, n->cin_pad, d.conv_bias, W, b);
-    if (int r = upload_layer(n->in, W, b, F, 9 * n->cin_pad, 9, n->cin_pad, pk.in16)) return r;  // 16-bit copies: g8 input conv
+    if (int r = upload_layer(n, n->in, W, b, F, 9 * n->cin_pad, 9, n->cin_pad, pk.in16)) return r;  // 16-bit copies: g8 input conv
     if (pk.in32) {
         std::vector<float> W32((size_t)F * 9 * 32, 0.0f);   // [F][9][32]: channels 16..31 zero
         for (size_t ot = 0; ot < (size_t)F * 9; ++ot) std::copy(&W[ot * 16], &W[ot * 16] + 16, &W32[ot * 32]);
-        if (int r = upload_layer(n->in32, W32, b, F, 9 * 32, 9, 32, true)) return r;
+        if (int r = upload_layer(n, n->in32, W32, b, F, 9 * 32, 9, 32, true)) return r;
     }
     if (pk.sm) sm_add(W, b, n->cin_pad);
     n->blk.resize(2 * d.blocks);
     for (int i = 0; i < 2 * d.blocks; ++i) {
         fold_conv(pc, F, F, 3, F, d.conv_bias, W, b);
-        if (int r = upload_layer(n->blk[i], W, b, F, 9 * F, 9, F, pk.trunk16)) return r;
+        if (int r = upload_layer(n, n->blk[i], W, b, F, 9 * F, 9, F, pk.trunk16)) return r;
         if (pk.sm) sm_add(W, b, F);
     }
     if (pk.sm) {
         const size_t ne = smw.size();
-        if (!n->sm_W) {
-            DALLOC(n->sm_W, ne); DALLOC(n->sm_Wf, ne); DALLOC(n->sm_Wxh, ne); DALLOC(n->sm_Wxl, ne); DALLOC(n->sm_b, smb.size());
-            DALLOC(n->sm_Wfh, ne); DALLOC(n->sm_Wfl, ne); DALLOC(n->sm_bx, smb.size()); DALLOC(n->sm_sx, smb.size());
-        }
+        WBUF(n->sm_W, ne); WBUF(n->sm_Wf, ne); WBUF(n->sm_Wxh, ne); WBUF(n->sm_Wxl, ne); WBUF(n->sm_b, smb.size());
+        WBUF(n->sm_Wfh, ne); WBUF(n->sm_Wfl, ne); WBUF(n->sm_bx, smb.size()); WBUF(n->sm_sx, smb.size());
         HIPCHK(hipMemcpy(n->sm_W, smw.data(), ne * 2, hipMemcpyHostToDevice));
         HIPCHK(hipMemcpy(n->sm_Wf, frag_major(smw, F).data(), ne * 2, hipMemcpyHostToDevice));
         HIPCHK(hipMemcpy(n->sm_Wxh, frag_major(smh, F).data(), ne * 2, hipMemcpyHostToDevice));
@@ -174,7 +174,7 @@ int load_heads(az_net* n, ParamCursor& pc) {
     const int F = d.channels, HC = d.head_channels, PP = d.pool * d.pool;
     std::vector<float> W, b;
     fold_conv(pc, HC, F, 1, F, d.conv_bias, W, b);
-    if (int r = upload_layer(n->pconv, W, b, HC, F, 1, F, false)) return r;
+    if (int r = upload_layer(n, n->pconv, W, b, HC, F, 1, F, false)) return r;
     std::vector<float> hW = W, hb = b;                 // the combined head conv, policy rows first
     auto fc = [&](int out, int hc, int pp, std::vector<float>& Wt, std::vector<float>& bt) {
         const float* w = pc.take((size_t)out * hc * pp);
@@ -183,20 +183,20 @@ int load_heads(az_net* n, ParamCursor& pc) {
         bt.assign(bb, bb + out);
     };
     fc(d.action_size, HC, PP, W, b);
-    if (int r = upload_layer(n->pfc, W, b, d.action_size, HC * PP, 1, HC * PP, false)) return r;
+    if (int r = upload_layer(n, n->pfc, W, b, d.action_size, HC * PP, 1, HC * PP, false)) return r;
     fold_conv(pc, HC, F, 1, F, d.conv_bias, W, b);
-    if (int r = upload_layer(n->vconv, W, b, HC, F, 1, F, false)) return r;
+    if (int r = upload_layer(n, n->vconv, W, b, HC, F, 1, F, false)) return r;
     hW.insert(hW.end(), W.begin(), W.end());
     hb.insert(hb.end(), b.begin(), b.end());
-    if (int r = upload_layer(n->hconv, hW, hb, 2 * HC, F, 1, F, false)) return r;
+    if (int r = upload_layer(n, n->hconv, hW, hb, 2 * HC, F, 1, F, false)) return r;
     fc(d.fc_hidden, HC, PP, W, b);
-    if (int r = upload_layer(n->vfc1, W, b, d.fc_hidden, HC * PP, 1, HC * PP, false)) return r;
+    if (int r = upload_layer(n, n->vfc1, W, b, d.fc_hidden, HC * PP, 1, HC * PP, false)) return r;
     {
         const float* w = pc.take(d.fc_hidden);
         const float* bb = pc.take(1);
         W.assign(w, w + d.fc_hidden);
         b.assign(bb, bb + 1);
-        if (int r = upload_layer(n->vfc2, W, b, 1, d.fc_hidden, 1, d.fc_hidden, false)) return r;
+        if (int r = upload_layer(n, n->vfc2, W, b, 1, d.fc_hidden, 1, d.fc_hidden, false)) return r;
     }
     // both FC layers as one matrix for k_fc_heads_x3 (wpack::fc_rows)
     {
@@ -205,10 +205,8 @@ int load_heads(az_net* n, ParamCursor& pc) {
         HIPCHK(hipMemcpy(Wp.data(), n->pfc.W, Wp.size() * 4, hipMemcpyDeviceToHost));
         HIPCHK(hipMemcpy(Wv.data(), n->vfc1.W, Wv.size() * 4, hipMemcpyDeviceToHost));
         const FcRows f = fc_rows(Wp.data(), A, Wv.data(), H, K);
-        if (!n->fcx_hi) {
-            DALLOC(n->fcx_hi, f.hi.size()); DALLOC(n->fcx_lo, f.lo.size());
-            DALLOC(n->fcf_hi, f.fh.size()); DALLOC(n->fcf_lo, f.fl.size()); DALLOC(n->fcf_rs, f.rs.size());
-        }
+        WBUF(n->fcx_hi, f.hi.size()); WBUF(n->fcx_lo, f.lo.size());
+        WBUF(n->fcf_hi, f.fh.size()); WBUF(n->fcf_lo, f.fl.size()); WBUF(n->fcf_rs, f.rs.size());
         HIPCHK(hipMemcpy(n->fcx_hi, f.hi.data(), f.hi.size() * 2, hipMemcpyHostToDevice));
         HIPCHK(hipMemcpy(n->fcx_lo, f.lo.data(), f.lo.size() * 2, hipMemcpyHostToDevice));
         HIPCHK(hipMemcpy(n->fcf_hi, f.fh.data(), f.fh.size() * 2, hipMemcpyHostToDevice));
@@ -227,9 +225,9 @@ int net_load_rw(az_net* n, const float* blob) {
     std::vector<float> W, b;
     const NetPacks pk = net_packs(net_shape(d, true));
     fold_conv(pc, F, d.in_planes, 3, n->cin_pad, false, W, b);
-    if (int r = upload_layer(n->in, W, b, F, 9 * n->cin_pad, 9, n->cin_pad, pk.in16)) return r;
+    if (int r = upload_layer(n, n->in, W, b, F, 9 * n->cin_pad, 9, n->cin_pad, pk.in16)) return r;
     auto raw = [&](float** dst, size_t cnt) -> int {
-        if (!*dst) DALLOC(*dst, cnt);
+        WBUF(*dst, cnt);
         HIPCHK(hipMemcpy(*dst, pc.take(cnt), cnt * 4, hipMemcpyHostToDevice));
         return 0;
     };
@@ -239,15 +237,15 @@ int net_load_rw(az_net* n, const float* blob) {
             const int deg = (int)pl.preds[v].size();
             if (!deg) continue;
             fold_conv(pc, F, deg * F, 1, deg * F, false, W, b);
-            if (int r = upload_layer(blk.node[v].router, W, b, F, deg * F, 1, deg * F, false)) return r;
+            if (int r = upload_layer(n, blk.node[v].router, W, b, F, deg * F, 1, deg * F, false)) return r;
         }
         for (int v : pl.order) {
             RwNode& nd = blk.node[v];
             const bool h16 = pk.trunk16;    // 16-bit weight copies: the node convs on conv3x3_v4
             fold_conv(pc, F, F, 3, F, false, W, b);
-            if (int r = upload_layer(nd.c1, W, b, F, 9 * F, 9, F, h16)) return r;
+            if (int r = upload_layer(n, nd.c1, W, b, F, 9 * F, 9, F, h16)) return r;
             fold_conv(pc, F, F, 3, F, false, W, b);
-            if (int r = upload_layer(nd.c2, W, b, F, 9 * F, 9, F, h16)) return r;
+            if (int r = upload_layer(n, nd.c2, W, b, F, 9 * F, 9, F, h16)) return r;
             if (int r = raw(&nd.w1, (size_t)R * F)) return r;
             if (int r = raw(&nd.b1, R)) return r;
             if (int r = raw(&nd.w2, (size_t)F * R)) return r;
@@ -256,7 +254,7 @@ int net_load_rw(az_net* n, const float* blob) {
         const int no = (int)pl.outputs.size();
         if (no > 1) {
             fold_conv(pc, F, no * F, 1, no * F, false, W, b);
-            if (int r = upload_layer(blk.out_router, W, b, F, no * F, 1, no * F, false)) return r;
+            if (int r = upload_layer(n, blk.out_router, W, b, F, no * F, 1, no * F, false)) return r;
         }
     }
     if (int r = load_heads(n, pc)) return r;
@@ -275,17 +273,16 @@ size_t net_blob_params(const az_net* n) {
 }
 
 // ---- net internals for dist.hip (engine_internal.h), C++ linkage
-int net_weight_buffers(az_net* n, std::vector<std::pair<void*, size_t>>& out) {
-    if (n->wbufs.empty()) {
-        // never loaded: a load of zero weights allocates (and records) every weight buffer, which a
-        // broadcast then overwrites (host work once per net, no device traffic beyond the uploads)
+int net_weight_buffers(az_net* n, std::vector<DevPool::Buf>& out) {
+    if (!n->loaded) {
+        // no load completed: a load of zero weights allocates every weight buffer still missing, which
+        // a broadcast then overwrites (host work once per net, no device traffic beyond the uploads)
         std::vector<float> zero(n->nparams, 0.0f);
-        WeightRegistry reg(&n->wbufs);
         if (int r = n->rw ? net_load_rw(n, zero.data()) : net_load(n, zero.data())) return r;
         HIPCHK(hipDeviceSynchronize());
         n->loaded = false;
     }
-    out = n->wbufs;
+    out = n->weights.bufs;
     return 0;
 }
 const std::vector<float>& net_host_blob(az_net* n) { return n->host_blob; }
@@ -310,11 +307,7 @@ int az_net_load_weights(az_net* n, const float* blob, size_t count) {
     if (count != n->nparams) return az_fail(AZ_ERR_ARG, "expected %zu parameters, got %zu", n->nparams, count);
     std::lock_guard<std::mutex> lk(n->mu);
     HIPCHK(hipSetDevice(n->e->device));
-    {
-        // the first load allocates the weight buffers: record them (net_weight_buffers)
-        WeightRegistry reg(n->wbufs.empty() ? &n->wbufs : nullptr);
-        if (int r = n->rw ? net_load_rw(n, blob) : net_load(n, blob)) return r;
-    }
+    if (int r = n->rw ? net_load_rw(n, blob) : net_load(n, blob)) return r;
     HIPCHK(hipDeviceSynchronize());   // null-stream uploads done before the non-blocking stream reads them
     n->host_blob.assign(blob, blob + count);
     return 0;

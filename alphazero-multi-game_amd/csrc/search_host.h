@@ -13,6 +13,7 @@ struct az_net;
 
 struct az_search {
     az_engine* e = nullptr;
+    DevPool pool;   // every device buffer of the handle: the pointers below and in `t` point into it
     az_net* net = nullptr;
     // az_search_set_slot_nets: slot g is evaluated by nets[slot_net[g]] (n_nets = 0: the one net above).
     // Net k's batch is region k of the batch buffers -- rows [k * G, (k + 1) * G) of t.eval_games,
@@ -65,9 +66,9 @@ struct az_search {
     int sp_next_id = 0;             // one past the highest game id started on the handle (az_selfplay_step restarts)
     // device-resident copies of the TreeDev variants the per-step kernels take (tree_dev()): those
     // kernels get one 8-byte pointer instead of the ~550-byte struct by value, on ~38k dispatches per
-    // C3 move.  Slot i's host shadow (pinned, the source of its async upload) is h_tree[i].
+    // C3 move.  Slot i's host shadow (pinned, the source of its async upload) is h_tree.p[i].
     TreeDev* d_tree = nullptr;
-    TreeDev* h_tree = nullptr;
+    Pinned<TreeDev> h_tree;
     int n_tree = 0, next_tree = 0;
     int64_t tree_evictions = 0;     // slot reuses (each a stream synchronisation): az_diag_tree_evictions
     // Dirichlet draws of the NEXT move, made on a host thread while the device searches this one

@@ -9,6 +9,7 @@
 #include <cstring>
 #include <functional>
 #include <future>
+#include <memory>
 #include <mutex>
 #include <random>
 #include <sstream>
@@ -41,7 +42,7 @@ constexpr int AZ_TREE_SLOTS = 16;
 // Variants repeat (2 arenas x {search, identity batch}), so uploads happen at the first moves only.
 const TreeDev* tree_dev(az_search* s, const TreeDev& t) {
     for (int i = 0; i < s->n_tree; ++i)
-        if (std::memcmp(&s->h_tree[i], &t, sizeof(TreeDev)) == 0) return s->d_tree + i;
+        if (std::memcmp(&s->h_tree.p[i], &t, sizeof(TreeDev)) == 0) return s->d_tree + i;
     int k;
     if (s->n_tree < AZ_TREE_SLOTS) {
         k = s->n_tree++;
@@ -51,8 +52,8 @@ const TreeDev* tree_dev(az_search* s, const TreeDev& t) {
         k = s->next_tree;
         s->next_tree = (k + 1) % AZ_TREE_SLOTS;
     }
-    std::memcpy(&s->h_tree[k], &t, sizeof(TreeDev));
-    if (hipMemcpyAsync(s->d_tree + k, &s->h_tree[k], sizeof(TreeDev), hipMemcpyHostToDevice, s->e->stream) != hipSuccess)
+    std::memcpy(&s->h_tree.p[k], &t, sizeof(TreeDev));
+    if (hipMemcpyAsync(s->d_tree + k, &s->h_tree.p[k], sizeof(TreeDev), hipMemcpyHostToDevice, s->e->stream) != hipSuccess)
         return nullptr;
     return s->d_tree + k;
 }
@@ -566,7 +567,8 @@ int search_create(az_engine* e, az_net* net, const az_search_cfg* c, int net_bat
         return az_fail(AZ_ERR_ARG, "prior_ring %d is smaller than one policy (%d entries)", c->prior_ring, NA);
     std::lock_guard<std::mutex> lk(e->mu);
     HIPCHK(hipSetDevice(e->device));
-    auto* s = new az_search();
+    std::unique_ptr<az_search, void (*)(az_search*)> guard(new az_search(), az_search_destroy);   // every early return frees it
+    az_search* s = guard.get();
     s->e = e; s->net = net; s->c = *c;
     const int ncap = c->node_capacity > 0 ? c->node_capacity : 3 * std::max(64, c->num_simulations) * NA + 8 * NA + 64;
     const int ring = c->prior_ring > 0 ? c->prior_ring : std::max(1 << 16, 12 * std::max(64, c->num_simulations) * NA);
@@ -579,7 +581,7 @@ int search_create(az_engine* e, az_net* net, const az_search_cfg* c, int net_bat
     t.stamp_game = g_tree_stamp_game;   // diagnostic phase stamps (az_diag_set_tree_stamps)
     const size_t NG = (size_t)G * ncap;
     int r = 0;
-#define SA(p, n) do { if (!r) r = dalloc(&(p), (size_t)(n)); } while (0)
+#define SA(p, n) do { if (!r) r = s->pool.alloc(&(p), (size_t)(n)); } while (0)
     for (int k = 0; k < 2; ++k) {
         Nodes& nd = s->arena[k];
         SA(nd.N, NG); SA(nd.W, NG); SA(nd.VL, NG); SA(nd.P, NG); SA(nd.first, NG); SA(nd.act, NG); SA(nd.cnt, NG);
@@ -587,7 +589,7 @@ int search_create(az_engine* e, az_net* net, const az_search_cfg* c, int net_bat
     }
     SA(t.atop, G); SA(t.rboard, (size_t)G * A); SA(t.rhist, G * 6); SA(t.rplayer, G); SA(t.rstones, G); SA(t.rply, G);
     SA(t.rhash, G); SA(t.rfresh, G); SA(t.rnode, G); SA(t.active, G); SA(t.gresult, G);
-    uint64_t* zko = nullptr;
+    uint64_t *zko = nullptr, *zp = nullptr, *zpl = nullptr; int* fo = nullptr;   // the TreeDev's const tables, filled below
     if (go) { SA(t.rko, G); SA(t.rpass, G); SA(t.rposh, (size_t)G * t.hmax); SA(t.rnposh, G); SA(zko, A + 1); }
     SA(t.path, (size_t)G * AZ_DMAX); SA(t.pact, (size_t)G * AZ_DMAX); SA(t.pstat, (size_t)G * AZ_DMAX); SA(t.rhdr, G); SA(t.plen, G); SA(t.lstatus, G); SA(t.lvalue, G); SA(t.lhash, G); SA(t.ttstore, G);
     SA(t.ttref, G); SA(t.tthslot, G); SA(t.need_eval, G); SA(t.eval_slot, G); SA(t.eval_games, G); SA(t.n_eval, 1);
@@ -597,7 +599,6 @@ int search_create(az_engine* e, az_net* net, const az_search_cfg* c, int net_bat
     SA(t.tt_ref, (size_t)G * t.tt_slots);
     SA(t.ring_buf, (size_t)G * ring); SA(t.ring_cur, G); SA(t.cnt, (size_t)G * AZ_NCNT);
     if (!r) r = hipMemset(t.cnt, 0, (size_t)G * AZ_NCNT * 8) == hipSuccess ? 0 : az_fail(AZ_ERR_HIP, "memset");
-    uint64_t* zp = nullptr; uint64_t* zpl = nullptr; int* fo = nullptr;
     SA(zp, 2 * A); SA(zpl, 2); SA(fo, A);
     if (c->eval_kind == AZ_EVAL_RANDOM) SA(t.mt, (size_t)G * 625);
     SA(t.err, 1);
@@ -611,7 +612,7 @@ int search_create(az_engine* e, az_net* net, const az_search_cfg* c, int net_bat
     SA(s->d_cact, (size_t)G * NA); SA(s->d_nch, G); SA(s->d_term, G); SA(s->d_res, G); SA(s->d_rexp, G); SA(s->d_games, G); SA(s->d_seed_ids, G); SA(s->d_temps, G);
     SA(s->d_rc, 4 * (size_t)NA + 8); SA(s->d_rcf, 2 * (size_t)NA + 4); SA(s->d_thr, G); SA(s->d_pruned, G);
 #undef SA
-    if (r) { az_search_destroy(s); return r; }
+    if (r) return r;
     t.zpiece = zp; t.zplayer = zpl; t.fresh_order = fo; t.zko = zko;
     if (s->d_id) {
         std::vector<int> id(G + 1);
@@ -649,11 +650,7 @@ int search_create(az_engine* e, az_net* net, const az_search_cfg* c, int net_bat
         HIPCHK(hipMemcpy(fo, order.data(), A * 4, hipMemcpyHostToDevice));
     }
     HIPCHK(hipMemset(t.err, 0, 4));
-    if (hipMalloc((void**)&s->d_tree, AZ_TREE_SLOTS * sizeof(TreeDev)) != hipSuccess ||
-        hipHostMalloc((void**)&s->h_tree, AZ_TREE_SLOTS * sizeof(TreeDev), hipHostMallocDefault) != hipSuccess) {
-        az_search_destroy(s);
-        return az_fail(AZ_ERR_OOM, "TreeDev slots");
-    }
+    if (s->pool.alloc(&s->d_tree, AZ_TREE_SLOTS) || !s->h_tree.get(AZ_TREE_SLOTS)) return az_fail(AZ_ERR_OOM, "TreeDev slots");
     HIPCHK(hipDeviceSynchronize());   // the null-stream copies / memsets above, before the engine stream runs
     // every slot an idle game with a valid root until k_new_games starts it
     t.nd = s->arena[0];
@@ -663,44 +660,20 @@ int search_create(az_engine* e, az_net* net, const az_search_cfg* c, int net_bat
     s->stones.assign(G, 0); s->active.assign(G, 0); s->fresh.assign(G, 1); s->ply.assign(G, 0); s->expanded.assign(G, 0);
     s->rng.resize(G);
     s->hist.assign(G, {});
-    if (!s->h_noise.get((size_t)G * NA)) { az_search_destroy(s); return az_fail(AZ_ERR_OOM, "hipHostMalloc (noise)"); }
+    if (!s->h_noise.get((size_t)G * NA)) return az_fail(AZ_ERR_OOM, "hipHostMalloc (noise)");
     std::fill(s->h_noise.p, s->h_noise.p + (size_t)G * NA, 0.0f);
     s->h_mask.assign(G, 0);
-    *out = s;
+    *out = guard.release();
     return 0;
 }
 
 extern "C" {
 
 void az_search_destroy(az_search* s) {
-    if (s) { pf_wait(s); s->pc.release(); s->pcf.release(); }
     if (!s) return;
+    pf_wait(s);
     (void)hipSetDevice(s->e->device);
-    auto F = [](const void* p) { if (p) (void)hipFree((void*)p); };
-    for (auto& nd : s->arena) { F(nd.N); F(nd.W); F(nd.VL); F(nd.P); F(nd.first); F(nd.act); F(nd.cnt); F(nd.flag); }
-    TreeDev& t = s->t;
-    for (const void* p : {(const void*)t.atop, (const void*)t.rboard, (const void*)t.rhist, (const void*)t.rplayer,
-                          (const void*)t.rstones, (const void*)t.rply, (const void*)t.rhash, (const void*)t.rfresh,
-                          (const void*)t.rnode, (const void*)t.active, (const void*)t.gresult, (const void*)t.path, (const void*)t.pact,
-                          (const void*)t.pstat, (const void*)t.rhdr,
-                          (const void*)t.plen, (const void*)t.lstatus, (const void*)t.lvalue, (const void*)t.lhash,
-                          (const void*)t.ttstore, (const void*)t.ttref, (const void*)t.tthslot, (const void*)t.need_eval,
-                          (const void*)t.eval_slot, (const void*)t.eval_games, (const void*)t.n_eval, (const void*)t.leafrec, (const void*)t.goleaf,
-                          (const void*)t.tt_hash, (const void*)t.tt_visits, (const void*)t.tt_value, (const void*)t.tt_ref,
-                          (const void*)t.ring_buf, (const void*)t.ring_cur, (const void*)t.cnt, (const void*)t.zpiece,
-                          (const void*)t.zplayer, (const void*)t.fresh_order, (const void*)t.mt, (const void*)t.err,
-                          (const void*)t.rko, (const void*)t.rpass, (const void*)t.rposh, (const void*)t.rnposh,
-                          (const void*)t.zko, (const void*)s->d_lmoves, (const void*)s->d_llen,
-                          (const void*)t.log_pol, (const void*)t.log_val, (const void*)t.log_planes, (const void*)t.log_n,
-                          (const void*)s->d_src_of, (const void*)s->d_batch, (const void*)s->d_id, (const void*)s->d_logits,
-                          (const void*)s->d_value, (const void*)s->d_noise, (const void*)s->d_mask, (const void*)s->d_actions,
-                          (const void*)s->d_values, (const void*)s->d_probs, (const void*)s->d_cact, (const void*)s->d_nch,
-                          (const void*)s->d_term, (const void*)s->d_res, (const void*)s->d_rexp, (const void*)s->d_games, (const void*)s->d_seed_ids, (const void*)s->d_temps,
-                          (const void*)s->d_rc, (const void*)s->d_rcf, (const void*)s->d_thr, (const void*)s->d_pruned,
-                          (const void*)s->d_tree, (const void*)s->d_slot_net})
-        F(p);
-    if (s->h_tree) (void)hipHostFree(s->h_tree);
-    delete s;
+    delete s;   // its pool frees every device buffer
 }
 
 int az_search_new_games(az_search* s, const int* games, int n) {
@@ -860,7 +833,12 @@ int az_search_root_children(az_search* s, int game, int* actions, int* N, int* V
     hipStream_t st = s->e->stream;
     const int A = s->t.NA;
     int *da, *dN, *dVL, *dn, *dri; float *dW, *dP, *drw;
-    DALLOC(da, A); DALLOC(dN, A); DALLOC(dVL, A); DALLOC(dn, 1); DALLOC(dri, 2); DALLOC(dW, A); DALLOC(dP, A); DALLOC(drw, 1);
+    DevPool tmp;   // freed on every return
+    int r = 0;
+#define TA(p, n) do { if (!r) r = tmp.alloc(&(p), (size_t)(n)); } while (0)
+    TA(da, A); TA(dN, A); TA(dVL, A); TA(dn, 1); TA(dri, 2); TA(dW, A); TA(dP, A); TA(drw, 1);
+#undef TA
+    if (r) return r;
     s->t.nd = s->arena[s->cur];
     hipLaunchKernelGGL(k_root_children, dim3(1), dim3(256), 0, st, s->t, game, da, dN, dVL, dW, dP, dn, dri, drw);
     int n = 0;
@@ -872,7 +850,6 @@ int az_search_root_children(az_search* s, int game, int* actions, int* N, int* V
     if (W) HIPCHK(hipMemcpy(W, dW, n * 4, hipMemcpyDeviceToHost));
     if (P) HIPCHK(hipMemcpy(P, dP, n * 4, hipMemcpyDeviceToHost));
     *n_children = n;
-    for (void* p : {(void*)da, (void*)dN, (void*)dVL, (void*)dn, (void*)dri, (void*)dW, (void*)dP, (void*)drw}) (void)hipFree(p);
     return 0;
 }
 
@@ -933,36 +910,34 @@ int az_search_set_slot_nets(az_search* s, az_net* const* nets, int n_nets, const
     int* games = nullptr; int* n_eval = nullptr; float* logits = nullptr; float* value = nullptr; float* batch = nullptr;
     uint8_t* sn = nullptr;
     const bool grow = n_nets > s->regions;
+    DevPool fresh;   // the new buffers, the handle's only once everything succeeded
     int r = 0;
     if (grow) {
         const size_t R = (size_t)n_nets;
-        if (!r) r = dalloc(&games, R * G);
-        if (!r) r = dalloc(&n_eval, R);
-        if (!r) r = dalloc(&logits, R * G * NA);
-        if (!r) r = dalloc(&value, R * G);
-        if (!r) r = dalloc(&batch, R * G * A * 16);
+        if (!r) r = fresh.alloc(&games, R * G);
+        if (!r) r = fresh.alloc(&n_eval, R);
+        if (!r) r = fresh.alloc(&logits, R * G * NA);
+        if (!r) r = fresh.alloc(&value, R * G);
+        if (!r) r = fresh.alloc(&batch, R * G * A * 16);
     }
-    if (!r) r = dalloc(&sn, (size_t)G);   // a fresh assignment buffer: a failed upload leaves the old one whole
+    if (!r) r = fresh.alloc(&sn, (size_t)G);   // a fresh assignment buffer: a failed upload leaves the old one whole
     hipError_t he = hipStreamSynchronize(st);   // no queued kernel reads the old buffers or the old assignment
     if (!r && he != hipSuccess) r = az_fail(AZ_ERR_HIP, "az_search_set_slot_nets: %s", hipGetErrorString(he));
     if (!r && grow && (hipMemset(games, 0, (size_t)n_nets * G * 4) != hipSuccess || hipMemset(n_eval, 0, (size_t)n_nets * 4) != hipSuccess))
         r = az_fail(AZ_ERR_HIP, "az_search_set_slot_nets: memset");
     if (!r && hipMemcpy(sn, slot_net, (size_t)G, hipMemcpyHostToDevice) != hipSuccess)
         r = az_fail(AZ_ERR_HIP, "az_search_set_slot_nets: slot_net upload");
-    if (r) {   // the handle as it was
-        for (void* p : {(void*)games, (void*)n_eval, (void*)logits, (void*)value, (void*)batch, (void*)sn})
-            if (p) (void)hipFree(p);
-        return r;
-    }
+    if (r) return r;   // the handle as it was
     if (grow) {
         for (void* p : {(void*)s->t.eval_games, (void*)s->t.n_eval, (void*)s->d_logits, (void*)s->d_value, (void*)s->d_batch})
-            if (p) (void)hipFree(p);
+            s->pool.release(p);
         s->t.eval_games = games; s->t.n_eval = n_eval;
         s->d_logits = logits; s->d_value = value; s->d_batch = batch;
         s->t.net_logits = logits; s->t.net_value = value;
         s->regions = n_nets;
     }
-    if (s->d_slot_net) (void)hipFree(s->d_slot_net);
+    s->pool.release(s->d_slot_net);
+    s->pool.adopt(fresh);
     s->d_slot_net = sn;
     for (int k = 0; k < AZ_MAX_SLOT_NETS; ++k) {
         s->nets[k] = k < n_nets ? nets[k] : nullptr;
@@ -1093,12 +1068,18 @@ int az_search_enable_eval_log(az_search* s, int game, int capacity) {
     std::lock_guard<std::mutex> lk(s->mu);
     HIPCHK(hipSetDevice(s->e->device));
     TreeDev& t = s->t;
-    if (t.log_pol) { (void)hipFree(t.log_pol); (void)hipFree(t.log_val); (void)hipFree(t.log_planes); (void)hipFree(t.log_n); }
-    t.log_pol = nullptr; t.log_val = nullptr; t.log_planes = nullptr; t.log_n = nullptr;
     const int npl = t.game == GAME_GO ? 8 : 11;
-    DALLOC(t.log_pol, (size_t)capacity * t.NA); DALLOC(t.log_val, capacity); DALLOC(t.log_planes, (size_t)capacity * npl * t.A);
-    DALLOC(t.log_n, 1);
-    HIPCHK(hipMemset(t.log_n, 0, 4));
+    // the new log in a pool of its own: a failure below leaves the old log whole and readable
+    DevPool fresh;
+    float *pol = nullptr, *val = nullptr, *planes = nullptr; int* cnt = nullptr;
+    if (int r = fresh.alloc(&pol, (size_t)capacity * t.NA)) return r;
+    if (int r = fresh.alloc(&val, capacity)) return r;
+    if (int r = fresh.alloc(&planes, (size_t)capacity * npl * t.A)) return r;
+    if (int r = fresh.alloc(&cnt, 1)) return r;
+    HIPCHK(hipMemset(cnt, 0, 4));
+    for (void* p : {(void*)t.log_pol, (void*)t.log_val, (void*)t.log_planes, (void*)t.log_n}) s->pool.release(p);
+    s->pool.adopt(fresh);
+    t.log_pol = pol; t.log_val = val; t.log_planes = planes; t.log_n = cnt;
     t.log_game = game; t.log_cap = capacity;
     return 0;
 }
@@ -1130,10 +1111,8 @@ int az_search_profile(az_search* s, int enable) {
     HIPCHK(hipStreamSynchronize(s->e->stream));
     s->prof = enable != 0;
     for (ProfClock* pc : {&s->pc, &s->pcf})
-        if (s->prof && !pc->d && hipMalloc((void**)&pc->d, ProfClock::CAP * 8) != hipSuccess) {
-            pc->d = nullptr;
-            return az_fail(AZ_ERR_OOM, "profile clock buffer");
-        }
+        if (s->prof)
+            if (int r = pc->enable(s->pool)) return r;
     s->pc.used = 0; s->pcf.used = 0;
     s->prof_steps = 0; s->prof_sampled = 0; s->prof_fused = 0; s->prof_fused_launches = 0;
     s->prof_cnt0.assign((size_t)s->c.n_games * AZ_NCNT, 0);

@@ -145,6 +145,13 @@ int az_net_trunk_kernel(az_net* n, char* name, int len);
  * family, tail and head FC variant, e.g. "in=g8/in32 trunk=g8 tail=fused heads=x3-bf16" (the route
  * table of DESIGN.md).  Needs neither a load nor a forward. */
 int az_diag_net_plan(az_net* n, char* out, int len);
+/* Diagnostic: the device memory every handle of the process holds right now -- payload bytes and
+ * buffers of all its pools (csrc/dev_pool.h).  A handle's create .. destroy leaves both unchanged. */
+int az_diag_device_mem(int64_t* bytes, int64_t* buffers);
+/* Diagnostic: nth >= 0 makes the nth device allocation from now (0: the next one) fail with
+ * AZ_ERR_OOM on the host, without touching the device, and disarms; -1 disarms.  Returns the
+ * countdown it replaced (-1: none was armed). */
+int az_diag_fail_alloc(int nth);
 /* predictBatch semantics: policy = softmax over A (max-subtracted, sequential fp32 sum,
  * torch_neural_network.cpp:296-316), value [B]. */
 int az_net_predict_batch(az_net* n, const float* planes, int B, float* policy, float* value);
