@@ -18,7 +18,7 @@ from dataclasses import dataclass, field
 
 import numpy as np
 
-from ._lib import (AZ_EVAL_CALLBACK, AZ_EVAL_HASH, AZ_EVAL_NET, AZ_EVAL_RANDOM, AZ_EVAL_UNIFORM, EVAL_FN, AZ_PREC_BF16, AZ_PREC_BF16X3, AZ_PREC_F16X3, AZ_PREC_F32, AZ_PREC_FP16, AzError,
+from ._lib import (AZ_GO_RULES_SET, AZ_EVAL_CALLBACK, AZ_EVAL_HASH, AZ_EVAL_NET, AZ_EVAL_RANDOM, AZ_EVAL_UNIFORM, EVAL_FN, AZ_PREC_BF16, AZ_PREC_BF16X3, AZ_PREC_F16X3, AZ_PREC_F32, AZ_PREC_FP16, AzError,
                    ARENA_SINK, ArenaCfg, ArenaSummary, GAME_SINK, PROGRESS_FN, MoveRec as _lib_MoveRec, NetDesc, SearchCfg, SelfPlayCfg, check, lib)
 
 __all__ = ["Engine", "HipNeuralNetwork", "ParallelMCTS", "SelfPlayManager", "Arena", "ArenaGameRecord", "EloRating", "GameRecord", "MoveData", "AzError",
@@ -203,15 +203,25 @@ class HipNeuralNetwork:
 AZ_GAME_GOMOKU, AZ_GAME_GO, AZ_ACTION_NONE = 0, 1, -2
 
 
+def _go_rules_fields(game, komi, chinese, superko):
+    """az_search_cfg's go_rules / go_komi / go_chinese_rules / go_superko: a Gomoku handle with the
+    default rules leaves them zero (the engine refuses any other rules on it)."""
+    if game != AZ_GAME_GO and (komi, bool(chinese), bool(superko)) == (7.5, True, True):
+        return 0, 0.0, 0, 0
+    return AZ_GO_RULES_SET, komi, int(bool(chinese)), int(bool(superko))
+
+
 class ParallelMCTS:
     """G independent ParallelMCTS trees (Mode S semantics, setDeterministicMode) on one device."""
 
     def __init__(self, engine, n_games=1, board_size=15, num_simulations=800, c_puct=1.5, fpu_reduction=0.0,
                  virtual_loss=3, evaluator=AZ_EVAL_HASH, net=None, eval_seed=7, zobrist_seed=12345, noise_seed=42,
                  noise_seed_stride=0, use_dirichlet_each_search=False, dirichlet_alpha=0.03, dirichlet_eps=0.25,
-                 tt_log2=20, node_capacity=0, prior_ring=0, game=0, callback=None):
-        """game: AZ_GAME_GOMOKU (0) or AZ_GAME_GO (1) -- GoState(bs 9/13/19, komi 7.5, Chinese rules,
-        superko); Go actions are -1 (pass) .. bs*bs-1 and finished games report AZ_ACTION_NONE.
+                 tt_log2=20, node_capacity=0, prior_ring=0, game=0, callback=None, go_komi=7.5, go_chinese_rules=True,
+                 go_superko=True):
+        """game: AZ_GAME_GOMOKU (0) or AZ_GAME_GO (1) -- GoState(bs 9/13/19, go_komi, go_chinese_rules,
+        go_superko), fixed for the handle's life; Go actions are -1 (pass) .. bs*bs-1 and finished games
+        report AZ_ACTION_NONE.
         evaluator=AZ_EVAL_CALLBACK: callback(games [n], moves: per leaf the moves from the empty board,
         planes [n][C][bs][bs]) -> (policy [n][NA] as NeuralNetwork::predict returns it, value [n])."""
         self.G = n_games
@@ -221,7 +231,8 @@ class ParallelMCTS:
         self.none = AZ_ACTION_NONE if game == AZ_GAME_GO else -1
         cfg = SearchCfg(n_games, board_size, num_simulations, c_puct, fpu_reduction, virtual_loss, evaluator,
                         eval_seed, zobrist_seed, noise_seed, noise_seed_stride, int(use_dirichlet_each_search),
-                        dirichlet_alpha, dirichlet_eps, tt_log2, node_capacity, prior_ring, game)
+                        dirichlet_alpha, dirichlet_eps, tt_log2, node_capacity, prior_ring, game,
+                        *_go_rules_fields(game, go_komi, go_chinese_rules, go_superko))
         self.cfg = cfg
         h = ctypes.c_void_p()
         check(lib().az_search_create(engine.h, net.h if net is not None else None, ctypes.byref(cfg), ctypes.byref(h)))
@@ -364,6 +375,12 @@ class ParallelMCTS:
         check(lib().az_search_root_children(self.h, game, _ip(act), _ip(N), _ip(VL), _fp(W), _fp(Pp), ctypes.byref(n)))
         k = n.value
         return act[:k], N[:k], VL[:k], W[:k], Pp[:k]
+
+    def goRules(self):
+        """(komi, chinese_rules, superko) the handle plays (az_search_go_rules)."""
+        k, c, sk = ctypes.c_float(), ctypes.c_int(), ctypes.c_int()
+        check(lib().az_search_go_rules(self.h, ctypes.byref(k), ctypes.byref(c), ctypes.byref(sk)))
+        return k.value, bool(c.value), bool(sk.value)
 
     def rootNode(self, game):
         N = ctypes.c_int()
@@ -603,11 +620,12 @@ class Arena:
     def __init__(self, engine, net_a, net_b, tables, board_size=15, num_simulations=800, swap_colors=False,
                  temperature=0.1, sample_moves=0, noise_alpha=0.03, noise_eps=0.0, game=0, c_puct=1.5,
                  fpu_reduction=0.0, virtual_loss=3, zobrist_seed=12345, noise_seed=42, noise_seed_stride=1, tt_log2=20,
-                 node_capacity=0, prior_ring=0):
+                 node_capacity=0, prior_ring=0, go_komi=7.5, go_chinese_rules=True, go_superko=True):
         self.tables, self.engine, self.nets = int(tables), engine, (net_a, net_b)
         self.cfg = SearchCfg(self.tables, board_size, num_simulations, c_puct, fpu_reduction, virtual_loss, AZ_EVAL_NET,
                              7, zobrist_seed, noise_seed, noise_seed_stride, 0, noise_alpha, noise_eps, tt_log2,
-                             node_capacity, prior_ring, game)
+                             node_capacity, prior_ring, game,
+                             *_go_rules_fields(game, go_komi, go_chinese_rules, go_superko))
         self.acfg = ArenaCfg(int(bool(swap_colors)), temperature, int(sample_moves), noise_alpha, noise_eps)
         h = ctypes.c_void_p()
         check(lib().az_arena_create(engine.h, net_a.h, net_b.h, ctypes.byref(self.cfg), ctypes.byref(self.acfg),

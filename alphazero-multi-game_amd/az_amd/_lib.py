@@ -35,7 +35,11 @@ class SearchCfg(ctypes.Structure):
                 ("fpu_reduction", c_float), ("virtual_loss", c_int), ("eval_kind", c_int), ("eval_seed", c_uint32),
                 ("zobrist_seed", c_uint32), ("noise_seed", c_uint32), ("noise_seed_stride", c_int),
                 ("use_dirichlet_each_search", c_int), ("dirichlet_alpha", c_float), ("dirichlet_eps", c_float),
-                ("tt_log2", c_int), ("node_capacity", c_int), ("prior_ring", c_int), ("game", c_int)]
+                ("tt_log2", c_int), ("node_capacity", c_int), ("prior_ring", c_int), ("game", c_int),
+                ("go_rules", c_int), ("go_komi", c_float), ("go_chinese_rules", c_int), ("go_superko", c_int)]
+
+
+AZ_GO_RULES_SET = 1
 
 
 class SelfPlayCfg(ctypes.Structure):
@@ -118,6 +122,7 @@ EXPORTS = {
     "az_search_set_rng": (c_int, [vp, c_int, vp]),
     "az_search_set_evaluator": (c_int, [vp, EVAL_FN, vp]),
     "az_search_set_params": (c_int, [vp, P(SearchCfg)]),
+    "az_search_go_rules": (c_int, [vp, P(c_float), P(c_int), P(c_int)]),
     "az_search_root_node": (c_int, [vp, c_int, P(c_int), P(c_int), P(c_float)]),
     "az_search_counters": (c_int, [vp, c_int, P(c_int64)]),
     "az_search_profile": (c_int, [vp, c_int]),

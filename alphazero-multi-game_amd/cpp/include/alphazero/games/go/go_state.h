@@ -5,8 +5,10 @@
 // illegal, positional superko over the positions after every stone move; game over after two
 // consecutive passes; area (Chinese) or territory (Japanese) scoring with komi; Zobrist keys of
 // ZobristHash(bs, 2, 2, 12345) plus the "ko_point" / "rules" / "komi" features; 8 enhanced
-// feature planes.  The device search implements the reference defaults (komi 7.5, Chinese rules,
-// superko): ParallelMCTS / SelfPlayManager refuse other settings.
+// feature planes.  Territory scoring credits each side with the opponent's captures, as the
+// reference does (go_rules.cpp:336-353).  The device search plays every combination: ParallelMCTS
+// and SearchGroup hand the state's komi, scoring and ko rule to their search handle;
+// createGameState and SelfPlayManager build the reference defaults (komi 7.5, Chinese, superko).
 #pragma once
 #include <utility>
 #include <vector>
@@ -48,6 +50,7 @@ class GoState : public core::IGameState {
     bool isChineseRules() const { return chinese_rules_; }
     bool isEnforcingSuperko() const { return superko_; }
     int getKoPoint() const { return ko_point_; }
+    int getConsecutivePasses() const { return consecutive_passes_; }
     std::pair<int, int> actionToCoord(int action) const;
     int coordToAction(int x, int y) const;
     std::pair<float, float> calculateScore() const;     // (black, white) incl. komi

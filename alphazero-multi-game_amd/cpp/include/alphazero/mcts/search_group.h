@@ -40,6 +40,8 @@ class ParallelMCTS;
 // evaluated by nn, with a table of tt's size (or config.transpositionTableSize), nGames slots.
 az_search_cfg makeSearchConfig(const MCTSConfig& config, const core::IGameState& state, nn::NeuralNetwork* nn,
                                const TranspositionTable* tt, int nGames);
+// Both configurations name the same Go rules (komi, scoring, ko rule), which a handle keeps for life.
+bool sameGoRules(const az_search_cfg& a, const az_search_cfg& b);
 
 class SearchGroup {
  public:

@@ -132,6 +132,9 @@ PYBIND11_MODULE(_alphazero_cpp, m) {
         .def("getCapturedStones", &go::GoState::getCapturedStones)
         .def("getKoPoint", &go::GoState::getKoPoint)
         .def("getKomi", &go::GoState::getKomi)
+        .def("isChineseRules", &go::GoState::isChineseRules)
+        .def("isEnforcingSuperko", &go::GoState::isEnforcingSuperko)
+        .def("getConsecutivePasses", &go::GoState::getConsecutivePasses)
         .def("calculateScore", &go::GoState::calculateScore);
 
     m.def("createGameState", &core::createGameState, py::arg("type"), py::arg("boardSize") = 0,

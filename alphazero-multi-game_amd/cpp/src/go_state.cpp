@@ -191,7 +191,9 @@ std::pair<float, float> GoState::calculateScore() const {   // go_rules.cpp:211-
         if (terr[p] == 1) b += 1.0f;
         else if (terr[p] == 2) w += 1.0f;
     }
-    if (!chinese_rules_) { b += (float)captured_[1]; w += (float)captured_[2]; }
+    // the reference credits each side with the OPPONENT's captures (go_rules.cpp:336-353: captured_[p]
+    // counts the stones player p captured); reproduced
+    if (!chinese_rules_) { b += (float)captured_[2]; w += (float)captured_[1]; }
     w += komi_;
     return {b, w};
 }

@@ -117,6 +117,8 @@ ParallelMCTS::ParallelMCTS(const core::IGameState& root, SearchGroup& group)
     config_.transpositionTableSize = 1 << g.tt_log2;
     if (root_->getBoardSize() != g.board_size || (root_->getGameType() == core::GameType::GO) != (g.game == AZ_GAME_GO))
         throw std::invalid_argument("ParallelMCTS: the root's game does not match the group's");
+    if (!sameGoRules(makeSearchConfig(config_, *root_, nn_, nullptr, 1), g))
+        throw std::invalid_argument("ParallelMCTS: the root's Go rules (komi, scoring, ko rule) differ from the group's");
     slot_ = group.acquire(*root_);
     group_ = &group;
     s_ = group.handle();
@@ -151,7 +153,20 @@ az_search_cfg makeSearchConfig(const MCTSConfig& config, const core::IGameState&
     int k = 0;
     while (((size_t)1 << k) < ttsize && k < 24) ++k;
     c.tt_log2 = k;
+    // the state's rules are the handle's: the device plays what the host state (and every replay of
+    // it: the rebuild, the callback evaluator's leaves, a group member) plays
+    if (auto* g = dynamic_cast<const go::GoState*>(&state)) {
+        c.go_rules = AZ_GO_RULES_SET;
+        c.go_komi = g->getKomi();
+        c.go_chinese_rules = g->isChineseRules() ? 1 : 0;
+        c.go_superko = g->isEnforcingSuperko() ? 1 : 0;
+    }
     return c;
+}
+
+bool sameGoRules(const az_search_cfg& a, const az_search_cfg& b) {
+    return a.go_rules == b.go_rules && a.go_komi == b.go_komi && a.go_chinese_rules == b.go_chinese_rules &&
+           a.go_superko == b.go_superko;
 }
 
 az_search_cfg ParallelMCTS::deviceConfig() const { return makeSearchConfig(config_, *root_, nn_, tt_, 1); }
@@ -167,7 +182,7 @@ static bool sameSearch(const az_search_cfg& a, const az_search_cfg& b) {   // al
            a.c_puct == b.c_puct && a.fpu_reduction == b.fpu_reduction && a.virtual_loss == b.virtual_loss &&
            a.eval_kind == b.eval_kind && a.eval_seed == b.eval_seed &&
            a.use_dirichlet_each_search == b.use_dirichlet_each_search && a.dirichlet_alpha == b.dirichlet_alpha &&
-           a.dirichlet_eps == b.dirichlet_eps && a.tt_log2 == b.tt_log2;
+           a.dirichlet_eps == b.dirichlet_eps && a.tt_log2 == b.tt_log2 && sameGoRules(a, b);
 }
 
 // The reference's setters change config_ and keep the tree (parallel_mcts.h:172-182); the device
@@ -186,11 +201,7 @@ void ParallelMCTS::applyConfig() {
 void ParallelMCTS::rebuild() {
     const bool go = root_->getGameType() == core::GameType::GO;
     if (!go && root_->getGameType() != core::GameType::GOMOKU) throw std::invalid_argument("ParallelMCTS: Gomoku or Go");
-    if (go) {
-        auto* g = dynamic_cast<const go::GoState*>(root_.get());
-        if (!g || g->getKomi() != 7.5f || !g->isChineseRules() || !g->isEnforcingSuperko())
-            throw std::invalid_argument("ParallelMCTS: the device Go rules are komi 7.5, Chinese rules, superko");
-    }
+    if (go && !dynamic_cast<const go::GoState*>(root_.get())) throw std::invalid_argument("ParallelMCTS: a Go root must be a GoState");
     // rng_ survives the rebuild (the reference's setters leave it alone): carried over whole
     std::vector<uint32_t> rng;
     if (s_) {

@@ -21,11 +21,7 @@ SearchGroup::SearchGroup(nn::NeuralNetwork* nn, const MCTSConfig& config, const 
     if (capacity < 1) throw std::invalid_argument("SearchGroup: capacity >= 1");
     const bool go = prototype.getGameType() == core::GameType::GO;
     if (!go && prototype.getGameType() != core::GameType::GOMOKU) throw std::invalid_argument("SearchGroup: Gomoku or Go");
-    if (go) {
-        auto* g = dynamic_cast<const go::GoState*>(&prototype);
-        if (!g || g->getKomi() != 7.5f || !g->isChineseRules() || !g->isEnforcingSuperko())
-            throw std::invalid_argument("SearchGroup: the device Go rules are komi 7.5, Chinese rules, superko");
-    }
+    if (go && !dynamic_cast<const go::GoState*>(&prototype)) throw std::invalid_argument("SearchGroup: a Go prototype must be a GoState");
     const DeviceEvaluator ev = deviceEvaluator(nn);
     if (ev.kind == AZ_EVAL_CALLBACK)
         throw std::invalid_argument("SearchGroup: host-callback evaluators are not grouped (HipNeuralNetwork, "

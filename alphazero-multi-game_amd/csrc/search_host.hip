@@ -6,6 +6,7 @@
 #include <sched.h>
 
 #include <algorithm>
+#include <cmath>
 #include <cstring>
 #include <functional>
 #include <future>
@@ -544,6 +545,16 @@ int az_search_create(az_engine* e, az_net* net, const az_search_cfg* c, az_searc
 
 }  // extern "C"
 
+// The Go rules a configuration names: go_rules 0 is GoState's defaults, whatever the other fields hold
+namespace {
+struct GoRules { float komi; int chinese, superko; };
+GoRules go_rules_of(const az_search_cfg& c) {
+    if (!c.go_rules) return {7.5f, 1, 1};
+    return {c.go_komi, c.go_chinese_rules != 0, c.go_superko != 0};
+}
+bool same_rules(const GoRules& a, const GoRules& b) { return a.komi == b.komi && a.chinese == b.chinese && a.superko == b.superko; }
+}  // namespace
+
 // az_search_create with the batch capacity asked of `net` given apart from the number of games: the
 // arena's handle (arena.hip) gives each of its two nets half of its slots at once.
 int search_create(az_engine* e, az_net* net, const az_search_cfg* c, int net_batch, az_search** out) {
@@ -556,6 +567,12 @@ int search_create(az_engine* e, az_net* net, const az_search_cfg* c, int net_bat
         return az_fail(AZ_ERR_ARG, "unsupported search configuration");
     if (go && bs != 9 && bs != 13 && bs != 19)
         return az_fail(AZ_ERR_ARG, "Go board %d: GoState supports 9, 13 and 19 (go_state.cpp:24-26)", bs);
+    if (c->go_rules != 0 && c->go_rules != AZ_GO_RULES_SET) return az_fail(AZ_ERR_ARG, "go_rules %d: 0 or AZ_GO_RULES_SET", c->go_rules);
+    const GoRules rules = go_rules_of(*c);
+    if (!std::isfinite(rules.komi) || std::fabs(rules.komi) > 1024.0f)
+        return az_fail(AZ_ERR_ARG, "go_komi must be finite with |komi| <= 1024");
+    if (!go && !same_rules(rules, GoRules{7.5f, 1, 1}))
+        return az_fail(AZ_ERR_ARG, "Go rules (komi / scoring / ko rule) on a Gomoku handle");
     if (c->eval_kind == AZ_EVAL_NET) {
         if (!net) return az_fail(AZ_ERR_ARG, "AZ_EVAL_NET needs a network");
         if (net->d.board_size != bs || net->d.action_size != NA || net->d.in_planes != (go ? 8 : 11))
@@ -578,6 +595,7 @@ int search_create(az_engine* e, az_net* net, const az_search_cfg* c, int net_bat
     t.hmax = go ? 2048 : 0; t.vl = c->virtual_loss; t.cpuct = c->c_puct; t.fpu = c->fpu_reduction;
     t.eval_kind = c->eval_kind; t.tt_slots = 1 << c->tt_log2; t.tt_mask = (uint64_t)t.tt_slots - 1; t.ring = ring;
     t.log_game = -1; t.log_cap = 0;
+    t.komi = rules.komi; t.chinese = rules.chinese; t.superko = rules.superko;
     t.stamp_game = g_tree_stamp_game;   // diagnostic phase stamps (az_diag_set_tree_stamps)
     const size_t NG = (size_t)G * ncap;
     int r = 0;
@@ -590,7 +608,7 @@ int search_create(az_engine* e, az_net* net, const az_search_cfg* c, int net_bat
     SA(t.atop, G); SA(t.rboard, (size_t)G * A); SA(t.rhist, G * 6); SA(t.rplayer, G); SA(t.rstones, G); SA(t.rply, G);
     SA(t.rhash, G); SA(t.rfresh, G); SA(t.rnode, G); SA(t.active, G); SA(t.gresult, G);
     uint64_t *zko = nullptr, *zp = nullptr, *zpl = nullptr; int* fo = nullptr;   // the TreeDev's const tables, filled below
-    if (go) { SA(t.rko, G); SA(t.rpass, G); SA(t.rposh, (size_t)G * t.hmax); SA(t.rnposh, G); SA(zko, A + 1); }
+    if (go) { SA(t.rko, G); SA(t.rpass, G); SA(t.rposh, (size_t)G * t.hmax); SA(t.rnposh, G); SA(t.rcap, 2 * (size_t)G); SA(zko, A + 1); }
     SA(t.path, (size_t)G * AZ_DMAX); SA(t.pact, (size_t)G * AZ_DMAX); SA(t.pstat, (size_t)G * AZ_DMAX); SA(t.rhdr, G); SA(t.plen, G); SA(t.lstatus, G); SA(t.lvalue, G); SA(t.lhash, G); SA(t.ttstore, G);
     SA(t.ttref, G); SA(t.tthslot, G); SA(t.need_eval, G); SA(t.eval_slot, G); SA(t.eval_games, G); SA(t.n_eval, 1);
     SA(t.leafrec, (size_t)G * AZ_REC_BYTES);
@@ -627,11 +645,11 @@ int search_create(az_engine* e, az_net* net, const az_search_cfg* c, int net_bat
         for (auto& k : ko) k = rk();
         HIPCHK(hipMemcpy(zko, ko.data(), (A + 1) * 8, hipMemcpyHostToDevice));
         std::mt19937_64 rr(std::hash<std::string>{}("rules"));
-        uint64_t rules[2] = {rr(), rr()};
+        uint64_t zrules[2] = {rr(), rr()};
         std::mt19937_64 rm(std::hash<std::string>{}("komi"));
         uint64_t komi[16];
         for (auto& k : komi) k = rm();
-        t.zconst = rules[1] ^ komi[((int)(7.5f * 2)) & 0xF];   // Chinese rules, komi 7.5
+        t.zconst = zrules[rules.chinese ? 1 : 0] ^ komi[((int)(rules.komi * 2)) & 0xF];   // updateHash (go_state.cpp:846-877)
     }
     t.net_logits = s->d_logits; t.net_value = s->d_value;
     // Zobrist keys: ZobristHash(bs, 2, 2, seed) (src/core/zobrist_hash.cpp:9-36)
@@ -974,6 +992,8 @@ int az_search_set_params(az_search* s, const az_search_cfg* c) {
         c->game != o.game || (c->node_capacity > 0 && c->node_capacity != o.node_capacity) ||
         (c->prior_ring > 0 && c->prior_ring != o.prior_ring) || c->num_simulations < 0 || c->virtual_loss < 0)
         return az_fail(AZ_ERR_ARG, "az_search_set_params: shape / evaluator / table changes need a new handle");
+    if ((c->go_rules != 0 && c->go_rules != AZ_GO_RULES_SET) || !same_rules(go_rules_of(*c), go_rules_of(o)))
+        return az_fail(AZ_ERR_ARG, "az_search_set_params: the Go rules are fixed for a handle's life");
     // the node pool and prior ring were sized for the creation's simulations per search
     const int NA = s->t.NA;
     if (3 * std::max(64, c->num_simulations) * NA + 8 * NA + 64 > o.node_capacity ||
@@ -986,6 +1006,13 @@ int az_search_set_params(az_search* s, const az_search_cfg* c) {
     s->c.dirichlet_alpha = c->dirichlet_alpha; s->c.dirichlet_eps = c->dirichlet_eps;
     s->c.noise_seed = c->noise_seed; s->c.noise_seed_stride = c->noise_seed_stride;
     s->t.cpuct = c->c_puct; s->t.fpu = c->fpu_reduction; s->t.vl = c->virtual_loss;
+    return 0;
+}
+
+int az_search_go_rules(az_search* s, float* komi, int* chinese_rules, int* superko) {
+    if (!s || !komi || !chinese_rules || !superko) return az_fail(AZ_ERR_ARG, "null argument");
+    const GoRules r = go_rules_of(s->c);
+    *komi = r.komi; *chinese_rules = r.chinese; *superko = r.superko;
     return 0;
 }
 

@@ -46,11 +46,16 @@ struct TreeDev {
     int* rplayer; int* rstones; int* rply; uint64_t* rhash; int* rfresh; int* rnode;
     int* active;                 // [G] game searching (not finished)
     // Go root state (GoState): ko point, consecutive passes, position_history_ (hashes of the
-    // positions after every stone move, go_state.cpp:250-252); rhash holds the stones-only hash
-    int* rko; int* rpass; uint64_t* rposh; int* rnposh; int hmax;
+    // positions after every stone move, go_state.cpp:250-252; kept under superko only); rhash holds
+    // the stones-only hash; rcap [G][2]: stones captured BY black / white (captured_stones_[1], [2])
+    int* rko; int* rpass; uint64_t* rposh; int* rnposh; int* rcap; int hmax;
     int pad0 = 0;                // explicit padding (zero): tree_dev() compares TreeDev variants bytewise
     const uint64_t* zko;         // [A + 1] "ko_point" feature keys
-    uint64_t zconst;             // "rules"[1] ^ "komi"[int(7.5*2) & 15] (Chinese rules, komi 7.5)
+    uint64_t zconst;             // "rules"[chinese] ^ "komi"[int(komi*2) & 15] (updateHash, with its & 15 aliasing)
+    // GoState(bs, komi, chinese_rules, enforce_superko), fixed for the handle's life: every branch
+    // on them is uniform over the grid
+    float komi; int chinese; int superko;
+    int pad3 = 0;
     int* gresult;                // [G] GameResult of the root state
     int* path; int* plen;        // [G][AZ_DMAX], [G]
     int* pact;                   // [G][AZ_DMAX] action of every path node (pact[0] unused)
@@ -79,6 +84,8 @@ struct TreeDev {
 };
 // no implicit padding: every byte of a TreeDev is a member (tree_dev() finds a variant with memcmp)
 static_assert(offsetof(TreeDev, zko) == offsetof(TreeDev, pad0) + sizeof(int), "TreeDev hole after pad0");
+static_assert(offsetof(TreeDev, gresult) == offsetof(TreeDev, pad3) + sizeof(int), "TreeDev hole after pad3");
+static_assert(offsetof(TreeDev, komi) == offsetof(TreeDev, zconst) + sizeof(uint64_t), "TreeDev hole before komi");
 static_assert(offsetof(TreeDev, leafrec) == offsetof(TreeDev, pad1) + sizeof(int), "TreeDev hole after pad1");
 static_assert(sizeof(TreeDev) == offsetof(TreeDev, pad2) + sizeof(int), "TreeDev tail padding");
 static_assert(offsetof(TreeDev, tt_mask) == 10 * sizeof(int), "TreeDev hole before tt_mask");

@@ -287,7 +287,7 @@ __device__ void write_leafrec(const TreeDev& t, int g, int lane, const uint8_t* 
 }
 
 // ---------------------------------------------------------------------------
-// Go (GoState as GoState(bs, 7.5, true, true): go_state.cpp / go_rules.cpp).  Rules code runs
+// Go (GoState(bs, t.komi, t.chinese, t.superko): go_state.cpp / go_rules.cpp).  Rules code runs
 // on lane 0 over the game's LDS board (a few hundred LDS operations per move; the network
 // forward of the same step is four orders of magnitude longer); per-point work is lane-parallel.
 struct GoLds {
@@ -299,6 +299,7 @@ struct GoLds {
     uint64_t phist[AZ_DMAX];     // position hashes pushed along the selection path
     uint64_t pkey[AZ_DMAX];      // piece key of the stone path move i places (go_build_leaf prefetch)
     int nph, stamp;
+    int cap[2];                  // stones captured by black / white up to the leaf (root counters + the path's)
 };
 
 __device__ __forceinline__ int go_adj(int pos, int bs, int A, int* nb) {   // getAdjacentPositions (:800-816)
@@ -321,8 +322,9 @@ __device__ void go_clear_marks(GoLds& L, int A, int lane) {
 // groups adjacent to the new stone can have none), ko point, stones hash.  Returns 1 when the
 // move pushes a position (stone moves), 0 for a pass.
 // key (optional): the placed stone's piece key, already loaded (go_build_leaf prefetches a path's keys)
+// cap (optional): capture counters {by black, by white}; the mover's grows by the stones removed
 __device__ int go_play_seq(const TreeDev& t, uint8_t* b, GoLds& L, int a, int p, int& ko, int& passes, uint64_t& bh,
-                           const uint64_t* key = nullptr) {
+                           const uint64_t* key = nullptr, int* cap = nullptr) {
     const int bs = t.bs, A = t.A;
     if (a < 0) { ++passes; ko = -1; return 0; }
     passes = 0;
@@ -362,6 +364,7 @@ __device__ int go_play_seq(const TreeDev& t, uint8_t* b, GoLds& L, int a, int p,
         }
     }
     ko = (ngroups == 1 && nstones == 1) ? last : -1;
+    if (cap) cap[p - 1] += nstones;
     return 1;
 }
 
@@ -442,15 +445,19 @@ __device__ void go_groups(const TreeDev& t, const uint8_t* b, GoLds& L, int tid,
     __syncthreads();
 }
 
-// GoRules::getTerritoryOwnership + calculateScores, Chinese rules (go_rules.cpp:211-361) ->
-// GameResult of a finished game (go_state.cpp:295-312).  Lane 0.
-__device__ int go_result_seq(const TreeDev& t, const uint8_t* b, GoLds& L) {
+// GoRules::getTerritoryOwnership + calculateScores (go_rules.cpp:211-361) -> GameResult of a finished
+// game (go_state.cpp:295-312).  Chinese rules: stones + territory; Japanese: territory + prisoners,
+// each side credited with the OPPONENT's captures as the reference does (:336-353); then the komi.
+// cap: stones captured by black / white.  Lane 0.
+__device__ int go_result_seq(const TreeDev& t, const uint8_t* b, GoLds& L, const int* cap) {
     const int bs = t.bs, A = t.A;
     float bsc = 0.0f, wsc = 0.0f;
     const int st = ++L.stamp;
-    for (int p0 = 0; p0 < A; ++p0) {
-        if (b[p0] == 1) { bsc += 1.0f; continue; }
-        if (b[p0] == 2) { wsc += 1.0f; continue; }
+    if (t.chinese) {
+        for (int p0 = 0; p0 < A; ++p0) {
+            if (b[p0] == 1) { bsc += 1.0f; continue; }
+            if (b[p0] == 2) { wsc += 1.0f; continue; }
+        }
     }
     for (int p0 = 0; p0 < A; ++p0) {
         if (b[p0] != 0 || L.mark[p0] == st) continue;
@@ -471,7 +478,8 @@ __device__ int go_result_seq(const TreeDev& t, const uint8_t* b, GoLds& L) {
         if (tb && !tw) bsc += (float)n;
         else if (tw && !tb) wsc += (float)n;
     }
-    wsc += 7.5f;
+    if (!t.chinese) { bsc += (float)cap[1]; wsc += (float)cap[0]; }
+    wsc += t.komi;
     if (bsc > wsc) return R_WIN1;
     if (wsc > bsc) return R_WIN2;
     return R_DRAW;
@@ -499,12 +507,14 @@ __device__ void go_build_leaf(const TreeDev& t, int g, int lane, const int* sact
         int p = t.rplayer[g], k = t.rko[g], ps = t.rpass[g];
         uint64_t h = t.rhash[g];
         int nph = 0;
+        int cap[2] = {t.rcap[2 * g], t.rcap[2 * g + 1]};
         for (int i = 1; i <= depth; ++i) {
             const int a = sact[i];
-            if (go_play_seq(t, board, L, a, p, k, ps, h, &L.pkey[i])) L.phist[nph++] = go_hash(t, h, p, k);
+            if (go_play_seq(t, board, L, a, p, k, ps, h, &L.pkey[i], cap)) L.phist[nph++] = go_hash(t, h, p, k);
             p = 3 - p;
         }
         L.nph = nph;
+        L.cap[0] = cap[0]; L.cap[1] = cap[1];
         L.list[0] = (int16_t)p; L.list[1] = (int16_t)k; L.list[2] = (int16_t)ps;
         L.gxor[0] = h;
     }
@@ -572,13 +582,13 @@ __device__ void go_write_leafrec(const TreeDev& t, int g, int lane, const uint8_
 
 // getLegalMoves (go_state.cpp:116-160): pass, then every empty non-ko point that is not suicide
 // (GoRules::isSuicidalMove) and whose resulting position -- same side to move, the old ko point --
-// is not in position_history_ (root history + the path's pushes).  Needs go_groups().
+// is not in position_history_ (root history + the path's pushes; enforce_superko only).  Needs go_groups().
 __device__ int go_legal(const TreeDev& t, int g, int lane, const uint8_t* b, const GoLds& L, int player, int ko,
                         uint64_t bh, int* legal, const GoKeys& K) {
     const int A = t.A, bs = t.bs;
     const int opp = 3 - player;
     const uint64_t* rh = t.rposh + (size_t)g * t.hmax;
-    const int nr = t.rnposh[g];
+    const int nr = t.superko ? t.rnposh[g] : 0;
     const uint64_t tail = t.zplayer[player - 1] ^ (ko >= 0 ? t.zko[ko] : 0ULL) ^ t.zconst;
     if (lane == 0) legal[0] = -1;
     int n = 1;
@@ -614,7 +624,7 @@ __device__ int go_legal(const TreeDev& t, int g, int lane, const uint8_t* b, con
         // positional superko, wave-uniform: every candidate against the root history (64 entries per
         // coalesced load, broadcast lane by lane -- not one dependent L2 round trip per entry) and
         // the path's pushes (LDS)
-        if (__ballot(ok)) {
+        if (t.superko && __ballot(ok)) {
             for (int r0 = 0; r0 < nr; r0 += 64) {
                 const uint64_t hv = r0 == 0 ? hv0 : (r0 + lane < nr ? rh[r0 + lane] : 0ULL);
                 const int m = min(64, nr - r0);
@@ -834,7 +844,7 @@ __device__ __forceinline__ void select_game(const TreeDev& t, int mode, const Ro
                 // GoState::isTerminal: two consecutive passes; area score (go_state.cpp:291-312)
                 if (gpass >= 2) {
                     int r = 0;
-                    if (lane == 0) r = go_result_seq(t, board, gl);
+                    if (lane == 0) r = go_result_seq(t, board, gl, gl.cap);
                     result = lane_bcast(r, 0);
                 }
             } else {
@@ -1520,7 +1530,8 @@ __global__ __launch_bounds__(64) void k_apply(TreeDev t, const int* actions, int
         if (lane == 0) {
             int pp = p, k = t.rko[g], ps = t.rpass[g];
             uint64_t bh = t.rhash[g];
-            if (go_play_seq(t, board, gl, a, pp, k, ps, bh)) {
+            int* cap = t.rcap + 2 * g;
+            if (go_play_seq(t, board, gl, a, pp, k, ps, bh, nullptr, cap) && t.superko) {   // simple ko keeps no history
                 const int n = t.rnposh[g];
                 if (n >= t.hmax) atomicOr(t.err, ERR_HIST);
                 else { t.rposh[(size_t)g * t.hmax + n] = go_hash(t, bh, pp, k); t.rnposh[g] = n + 1; }
@@ -1532,7 +1543,7 @@ __global__ __launch_bounds__(64) void k_apply(TreeDev t, const int* actions, int
             t.rstones[g] += a >= 0 ? 1 : 0;
             t.rply[g] += 1;
             t.rfresh[g] = 0;
-            const int res = ps >= 2 ? go_result_seq(t, board, gl) : R_ONGOING;
+            const int res = ps >= 2 ? go_result_seq(t, board, gl, cap) : R_ONGOING;
             t.gresult[g] = res;
             if (res != R_ONGOING) t.active[g] = 0;
             terminal[g] = res != R_ONGOING;
@@ -1734,7 +1745,7 @@ __global__ __launch_bounds__(64) void k_new_games(TreeDev t, const int* games, c
     if (lane == 0) {
         t.rplayer[g] = 1; t.rstones[g] = 0; t.rply[g] = 0; t.rfresh[g] = 1;
         t.rhash[g] = t.game == GAME_GO ? 0ULL : t.zplayer[0];   // Go: stones-only hash of the empty board
-        if (t.game == GAME_GO) { t.rko[g] = -1; t.rpass[g] = 0; t.rnposh[g] = 0; }
+        if (t.game == GAME_GO) { t.rko[g] = -1; t.rpass[g] = 0; t.rnposh[g] = 0; t.rcap[2 * g] = 0; t.rcap[2 * g + 1] = 0; }
         t.rnode[g] = 0; t.atop[g] = 1; t.active[g] = 1; t.gresult[g] = R_ONGOING; t.ring_cur[g] = 0;
         nd.N[0] = 0; nd.W[0] = 0.0f; nd.VL[0] = 0; nd.P[0] = 0.0f; nd.first[0] = -1; nd.act[0] = -1;
         nd.cnt[0] = 0; nd.flag[0] = 0;

@@ -183,15 +183,26 @@ typedef struct az_search_cfg {
     int tt_log2;          /* TranspositionTable slots = 2^tt_log2 per game (reference: 20) */
     int node_capacity;    /* per-game node pool (0: auto = sims*A + 4*A) */
     int prior_ring;       /* per-game prior ring floats for TT hits (0: auto) */
-    int game;             /* AZ_GAME_GOMOKU (0) or AZ_GAME_GO (1): GoState(bs, komi 7.5, Chinese rules,
-                             superko), bs 9/13/19, action space bs*bs + 1, pass = action -1.  For Go,
-                             az_search_select reports finished games as AZ_ACTION_NONE and
-                             az_search_apply skips them (Gomoku: -1, as before). */
+    int game;             /* AZ_GAME_GOMOKU (0) or AZ_GAME_GO (1): GoState(bs, komi, chinese_rules,
+                             enforce_superko) with the rules below, bs 9/13/19, action space bs*bs + 1,
+                             pass = action -1.  For Go, az_search_select reports finished games as
+                             AZ_ACTION_NONE and az_search_apply skips them (Gomoku: -1, as before). */
+    /* Go rules, fixed for the handle's life.  go_rules 0 (a zero-initialised struct): GoState's
+     * defaults -- komi 7.5, Chinese rules, positional superko -- and the three fields after it are
+     * ignored.  AZ_GO_RULES_SET: they hold.  Komi must be finite with |komi| <= 1024 (so that
+     * (int)(komi * 2), the hash's komi key index, is exact); a Gomoku handle takes only the defaults;
+     * az_search_set_params with other rules than the handle's is refused (all AZ_ERR_ARG). */
+    int go_rules;         /* 0 or AZ_GO_RULES_SET */
+    float go_komi;        /* added to White's score (GoRules::calculateScores) */
+    int go_chinese_rules; /* != 0: area scoring; 0: territory + prisoners, each side credited with the
+                             opponent's captures as the reference does (go_rules.cpp:336-353) */
+    int go_superko;       /* != 0: positional superko over the game's positions; 0: the ko point only */
 } az_search_cfg;
 
 #define AZ_GAME_GOMOKU 0
 #define AZ_GAME_GO 1
 #define AZ_ACTION_NONE (-2)   /* Go: no move (finished game); -1 is the pass */
+#define AZ_GO_RULES_SET 1
 
 int az_search_create(az_engine* e, az_net* net, const az_search_cfg* cfg, az_search** out);
 /* AZ_EVAL_CALLBACK: every simulation step hands the n leaves that need an evaluation to the host,
@@ -262,6 +273,9 @@ int az_search_root_node(az_search* s, int game, int* N, int* VL, float* W);
  * fpu_reduction, virtual_loss, the Dirichlet fields and the noise seeds of later new games.
  * Shape, evaluator and table changes need a new handle (AZ_ERR_ARG). */
 int az_search_set_params(az_search* s, const az_search_cfg* cfg);
+/* The Go rules the handle plays (the defaults spelled out when it was created with go_rules 0; a
+ * Gomoku handle reports the defaults): what a host object hands to the handle it rebuilds. */
+int az_search_go_rules(az_search* s, float* komi, int* chinese_rules, int* superko);
 /* Swap the device net of an AZ_EVAL_NET handle in place, trees kept (ParallelMCTS::
  * setNeuralNetwork, parallel_mcts.cpp:1190-1207, only replaces nn_): same engine, board, planes
  * and action space, max_batch >= n_games, weights loaded; else AZ_ERR_ARG / AZ_ERR_STATE. */
