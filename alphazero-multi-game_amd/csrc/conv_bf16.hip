@@ -1788,7 +1788,8 @@ int az_launch_pool_heads_g8(const uint16_t* hi, const int8_t* q, const float* Wt
 }
 
 static int g_conv_flags = 4 | 0x200;   // bit 2: v6 (16x16x32) at 15x15; 0x200: v7 on 15x15 boards only
-// Variant bits for A/B measurement inside one process (tools/net_bench.py --flags); none defined now
+// Variant bits for A/B measurement inside one process (tools/net_bench.py --flags): 0x2000 selects
+// conv3x3_v7's per-tap main loop on the SLIM tile (g8_choice below); no others defined now
 // (a residual L2 prefetch during the main loop measured 0.6% slower and was removed; a cross-row
 // fragment prefetch and a mid-row barrier variant measured 1.5-2% slower)
 extern "C" int az_diag_set_conv_flags(int flags) { g_conv_flags = flags; return 0; }
@@ -1825,7 +1826,9 @@ static int g8_choice(const ConvBf16Args& a, int* geo) {
     // flag 0x200: v7 only on 15x15 boards; 15x15 tile geometry: SLIM (default), flag 8 DENSE, 0x400 PAD.
     // 15x15 below 1024 boards: a launch is one or two rounds of blocks and v6 is faster (B = 256: 61
     // vs 65 us); the other boards take v7's small DENSE tiles there (next branch).  Flag 0x800 forces
-    // v7 at any batch.
+    // v7 at any batch.  Flag 0x2000: the SLIM tile keeps conv3x3_v7's per-tap main loop (weight ring in
+    // LDS, one barrier per tap) instead of the row-streamed one (conv_v7.hip; A/B measurement, read by
+    // the kernel itself: a wave-uniform branch between the two compiled loops).
     const int boards_g8 = a.M / (a.H * a.W);
     if (!(a.flags & 0x100) && (a.H == 15 || !(a.flags & 0x200)) && (boards_g8 >= 1024 || (a.flags & 0x800)) &&
         az_conv_v7_supported(a)) {

@@ -18,7 +18,12 @@
 //    stores straight from registers -- no LDS staging, no block barrier, each wave on its own;
 //  * one barrier per tap.  Weight tiles land 4 taps ahead; each barrier certifies the NEXT tap's
 //    tile, so every fragment of tap s+1 is read during tap s's MFMAs (no read latency after a
-//    barrier).  The halo of chunk c+1 is fetched during taps 0..4 of chunk c.
+//    barrier).  The halo of chunk c+1 is fetched during taps 0..4 of chunk c;
+//  * the SLIM 15x15 tile (the C3 trunk) runs a row-streamed main loop instead: the halo row pitch is
+//    one fragment, so each of 17 fragment rows x 3 column shifts is read from LDS once and multiplied
+//    into up to three output fragments; a wave owns the whole board x 32 channels and holds its tap
+//    weights of the chunk in registers, loaded straight from the packed weights.  Of the 72 KB only
+//    the halo double buffer (2 x 20 KB) is used, and there is one barrier per chunk (see the loop).
 //
 // Tile geometry (as v6): 15x15 boards use the padded grid (outputs on a 15x17 grid, one board per
 // 256-row tile, 225 of 256 rows live) or DENSE tiles; every other board uses DENSE tiles (256
@@ -121,6 +126,15 @@ __device__ __forceinline__ void ds_rd(F& d, uint32_t addr) {
 template <int N, typename F>
 __device__ __forceinline__ void lgkm(F (&x)[4]) {
     asm volatile("s_waitcnt lgkmcnt(%4)" : "+v"(x[0]), "+v"(x[1]), "+v"(x[2]), "+v"(x[3]) : "i"(N) : "memory");
+}
+
+template <int N, typename F>
+__device__ __forceinline__ void lgkm1(F& x) {          // the same for one fragment
+    asm volatile("s_waitcnt lgkmcnt(%1)" : "+v"(x) : "i"(N) : "memory");
+}
+template <int N>
+__device__ __forceinline__ void wait_vmc() {           // s_waitcnt vmcnt(N), N a compile-time constant
+    asm volatile("s_waitcnt vmcnt(%0)" ::"i"(N) : "memory");
 }
 
 __device__ __forceinline__ void wait_vm(int n) {      // s_waitcnt vmcnt(n), n wave-uniform
@@ -278,6 +292,229 @@ __global__ __launch_bounds__(256, RG == 3 ? 3 : 2) void conv3x3_v7(ConvBf16Args 
                                                      (int)lane16, so + b_src[j], 0, 0);
     };
 
+    const int l16 = lane & 15, lg = lane >> 4;
+
+    // epilogue, straight from the accumulators acc[NIE][NJ] of a wave tile of NIE fragment rows from
+    // output grid row q0 x NJ 16-channel operands from channel chl - 4*lg: lane holds channels
+    // chl + 16j + e of pixel l16 of every 16 x 16 tile; residual join, ReLU, 16-bit + int8 split,
+    // streaming stores
+    auto epilogue = [&](auto& acc, const int q0, const int chl) {
+    typedef typename std::remove_reference<decltype(acc)>::type AccT;
+    constexpr int NIE = std::extent<AccT, 0>::value, NJ = std::extent<AccT, 1>::value;
+    const __amdgpu_buffer_rsrc_t rh = __builtin_amdgcn_make_buffer_rsrc((void*)p.Rhi, (short)0, 0x7fffffff, 0x00020000);
+    const __amdgpu_buffer_rsrc_t rq = __builtin_amdgcn_make_buffer_rsrc((void*)p.Rq, (short)0, 0x7fffffff, 0x00020000);
+    float vmax = 0.0f;                                    // fp16: the largest output (the range guard)
+    auto locate = [&](int i, int& b, int& pix) -> bool {  // fragment row i of the lane: board, pixel, live
+        const int q = q0 + i * 16 + l16;                  // output grid row of the tile
+        if constexpr (DENSE) {
+            const int gq = tile * TM + q;
+            b = gq / HW;
+            pix = gq - b * HW;
+            return b < nboards;
+        } else {
+            const int y = q / WG, x = q - y * WG;
+            b = tile;
+            pix = y * HB + x;
+            return y < HB && x < HB;
+        }
+    };
+    // The residual join's loads go out EB fragment rows at a time (one memory round trip per burst,
+    // two per wave at NIE = 8, five at 15), not one round trip per row: each row's loads would
+    // otherwise wait behind the previous row's stores (the asm stores are memory barriers to the
+    // compiler), and a 2nd conv's epilogue was eight serial HBM round trips per wave (conv2 498 us
+    // vs conv1 423 us per C3 launch under PMC, profiles/r06_c3_fp16_pmc_calib.json).  <= 48 VGPRs per
+    // burst; the arithmetic and the stored values are unchanged.
+    constexpr int EB = NIE <= 4 ? NIE : NIE % 4 == 0 ? 4 : NIE % 3 == 0 ? 3 : NIE % 2 == 0 ? 2 : 1;
+    static_assert(NIE % EB == 0, "bursts");
+#pragma unroll
+    for (int i0 = 0; i0 < NIE; i0 += EB) {
+    u32x2_t hv[EB][NJ];
+    uint32_t qv[EB][NJ];
+    if (p.Rhi) {
+#pragma unroll
+        for (int ii = 0; ii < EB; ++ii) {
+            int b, pix;
+            if (!locate(i0 + ii, b, pix)) continue;
+#pragma unroll
+            for (int j = 0; j < NJ; ++j) {
+                const int ch = chl + j * 16;
+                const size_t e = (((size_t)b * GO + (ch >> 3)) * HW + pix) * 8 + (ch & 7);
+                hv[ii][j] = __builtin_amdgcn_raw_buffer_load_b64(rh, (int)(e * 2), 0, AZ_RES_AUX);
+                qv[ii][j] = __builtin_amdgcn_raw_buffer_load_b32(rq, (int)e, 0, AZ_RES_AUX);
+            }
+        }
+    }
+#pragma unroll
+    for (int ii = 0; ii < EB; ++ii) {
+        const int i = i0 + ii;
+        int b, pix;
+        if (!locate(i, b, pix)) continue;
+#pragma unroll
+        for (int j = 0; j < NJ; ++j) {
+            const int ch = chl + j * 16;
+            const size_t e = (((size_t)b * GO + (ch >> 3)) * HW + pix) * 8 + (ch & 7);
+            float o[4] = {acc[i][j][0], acc[i][j][1], acc[i][j][2], acc[i][j][3]};
+            if (p.Rhi) {
+                uint16_t hh[4];
+                int8_t qq[4];
+                __builtin_memcpy(hh, &hv[ii][j], 8);
+                __builtin_memcpy(qq, &qv[ii][j], 4);
+#pragma unroll
+                for (int k = 0; k < 4; ++k) o[k] += H::join(hh[k], qq[k]);
+            }
+            uint16_t oh[4];
+            int8_t oq[4];
+#pragma unroll
+            for (int k = 0; k < 4; ++k) {
+                o[k] = __builtin_amdgcn_fmed3f(o[k], 0.0f, 3.0e38f);   // ReLU
+                if constexpr (MODE == 2) vmax = __builtin_fmaxf(vmax, o[k]);
+                if (p.Cq) H::split(o[k], oh[k], oq[k]);
+                else oh[k] = H::from_f(o[k]);
+            }
+            u32x2_t hs;
+            __builtin_memcpy(&hs, oh, 8);
+            asm volatile("global_store_dwordx2 %0, %1, off" AZ_V7_ST ::"v"(p.Chi + e), "v"(hs) : "memory");
+            if (p.Cq) {
+                uint32_t qs;
+                __builtin_memcpy(&qs, oq, 4);
+                asm volatile("global_store_dword %0, %1, off" AZ_V7_ST ::"v"(p.Cq + e), "v"(qs) : "memory");
+            }
+        }
+    }
+    }
+    if (MODE == 2 && !(vmax <= 65504.0f) && p.ovf) atomicOr(p.ovf, 1);   // fp16 overflow: the engine fails the forward
+    };
+
+    // The row-streamed main loop (SLIM 15x15, 256-row tile, 4-slot geometry; the default there, conv
+    // flag 0x2000 keeps the per-tap loop below).  On the SLIM grid the halo row pitch WG is exactly one
+    // fragment (16 rows), so the fragment that output fragment i reads at tap (dy, dx) IS the fragment
+    // that output fragment i + dy reads at tap (0, dx): fragment row f = 0..16, shifted by dx, is read
+    // from LDS once and multiplied into acc[f] (tap row 0), acc[f-1] (tap row 1) and acc[f-2] (tap row
+    // 2) -- 51 fragment reads per chunk instead of 72 / 63.
+    //  * wave tile: all 15 live fragments of the board x 32 channels n0 + 32*wave + 16j (120
+    //    accumulator registers); no row halves, no dead 16th fragment, every wave does 270 MFMAs per chunk;
+    //  * the wave's weights of a chunk (9 taps x 2 operands, 72 registers) come straight from the
+    //    packed layout [C/16][9][2][N][8] by 16-B buffer loads (an operand is four 256-B runs, one per
+    //    8-channel group): no weight tiles in LDS, no weight DMA, and with the ring gone ONE block
+    //    barrier per chunk (the halo double buffer) instead of one per tap;
+    //  * the next chunk's weights roll in behind the last use of each tap row: W(0,.) is dead after
+    //    f = 14, W(1,.) after f = 15, W(2,.) after f = 16, and each row is reloaded right there;
+    //  * every accumulator still receives its nine taps in the order t = 3*dy + dx (f ascending is dy
+    //    ascending for a fixed output fragment), chunk after chunk, seeded by the bias: the result is
+    //    bitwise that of the per-tap loop and of conv3x3_v6.
+    // vmcnt counts the halo's DMA pieces and the weight loads together in issue order; the budgets
+    // below are compile-time constants (past the last chunk both are harmless reloads).
+    constexpr bool ROWS = SLIM && WG == 16 && TM == 256 && RG == 4;
+    if constexpr (ROWS) {
+        if (!(p.flags & 0x2000)) {
+            constexpr int NF = GM::NFRAG, NFR = NF + 2;   // 15 output fragments, 17 fragment rows of the halo
+            static_assert(NF == 15 && NRB == 5 && (NFR * 16 + 2) <= GM::TROWS, "row-streamed geometry");
+            f32x4v acc[NF][2];
+#pragma unroll
+            for (int j = 0; j < 2; ++j) {                 // the bias seeds the accumulators
+                const float4 bv = *reinterpret_cast<const float4*>(p.bias + n0 + wave * 32 + j * 16 + 4 * lg);
+#pragma unroll
+                for (int i = 0; i < NF; ++i) acc[i][j] = f32x4v{bv.x, bv.y, bv.z, bv.w};
+            }
+            // weight operand j of tap t of chunk c: rows n0 + 32*wave + 16j + l16 of the 16-channel
+            // blocks 2c + (lg >> 1), half lg & 1; lane part in a VGPR, the rest in the scalar offset
+            const int N16 = p.N * 16;
+            const uint32_t w_lane = (uint32_t)((18 * (lg >> 1) + (lg & 1)) * N16 + l16 * 16);
+            const int w_wave = (n0 + wave * 32) * 16;
+            frag W[3][3][2];
+            auto loadW = [&](int c, auto dyc) {           // tap row dy of chunk c
+                constexpr int dy = decltype(dyc)::value;
+#pragma unroll
+                for (int dx = 0; dx < 3; ++dx) {
+                    const int so = __builtin_amdgcn_readfirstlane((36 * c + 2 * (3 * dy + dx)) * N16 + w_wave);
+#pragma unroll
+                    for (int j = 0; j < 2; ++j) {
+                        const auto v = __builtin_amdgcn_raw_buffer_load_b128(rsB, (int)(w_lane + j * 256), so, 0);
+                        __builtin_memcpy(&W[dy][dx][j], &v, 16);
+                    }
+                }
+            };
+            using I0 = std::integral_constant<int, 0>;
+            using I1 = std::integral_constant<int, 1>;
+            using I2 = std::integral_constant<int, 2>;
+            // fragment (f, dx): halo rows 16f + dx + l16 of group lg (the top row read is 273 < TROWS)
+            const uint32_t a_lane = lds_addr(abuf) + lg * (HROWS * 16) + l16 * 16;
+            frag F[3];                                    // step k = 3f + dx lives in F[k % 3]
+
+            // prologue: halo of chunk 0, then the 18 weight loads of chunk 0
+#pragma unroll
+            for (int j = 0; j < NRB; ++j) issueA(j, 0, 0);
+            __builtin_amdgcn_sched_barrier(0);
+            loadW(0, I0{});
+            loadW(0, I1{});
+            loadW(0, I2{});
+            __builtin_amdgcn_sched_barrier(0);
+            wait_vmc<18>();                               // the halo landed; the weights may fly
+            __builtin_amdgcn_s_barrier();
+            __builtin_amdgcn_sched_barrier(0);
+            ds_rd<0 * 16>(F[0], a_lane);
+            ds_rd<1 * 16>(F[1], a_lane);
+            ds_rd<2 * 16>(F[2], a_lane);
+
+            for (int c = 0; c < NCH; ++c) {
+                const int cn = c + 1 < NCH ? c + 1 : c;   // the last chunk reloads itself
+                const uint32_t a_cur = a_lane + (c & 1) * A_BUF, a_nxt = a_lane + ((c + 1) & 1) * A_BUF;
+                static_for<0, 3 * NFR>([&](auto kc) {
+                    constexpr int k = decltype(kc)::value, f = k / 3, dx = k % 3, r = k % 3;
+                    constexpr int LAST = 3 * (NFR - 1);   // first step of the last fragment row
+                    if constexpr (k == LAST) {
+                        // every fragment read of this chunk has landed (none is issued after this point),
+                        // and so have this wave's pieces of the next halo: the six W(0,.) loads issued at
+                        // f = 15 are the only younger vector-memory operations.  Past the barrier every
+                        // wave is done with this chunk's halo buffer, which the next chunk's DMA overwrites,
+                        // and the next chunk's halo is complete.
+                        lgkm1<0>(F[0]);
+                        lgkm1<0>(F[1]);
+                        lgkm1<0>(F[2]);
+                        wait_vmc<6>();
+                        __builtin_amdgcn_s_barrier();
+                    } else {
+                        lgkm1<2>(F[r]);                   // fragments k + 1 and k + 2 stay in flight
+                    }
+                    __builtin_amdgcn_sched_barrier(0);
+                    // DMA: piece f of the next chunk's halo at f = 0..4; the next chunk's tap rows as they die
+                    if constexpr (dx == 0 && f < NRB) issueA(f, cn, (c + 1) & 1);
+                    if constexpr (k == 3 * NF) loadW(cn, I0{});
+                    if constexpr (k == LAST) loadW(cn, I1{});
+                    __builtin_amdgcn_sched_barrier(0);
+                    static_for<0, 3>([&](auto dyc) {
+                        constexpr int dy = decltype(dyc)::value, i = f - dy;
+                        if constexpr (i >= 0 && i < NF) {
+#pragma unroll
+                            for (int j = 0; j < 2; ++j) {
+                                if constexpr (MODE == 2)
+                                    acc[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_f16(W[dy][dx][j], F[r], acc[i][j], 0, 0, 0);
+                                else
+                                    acc[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(W[dy][dx][j], F[r], acc[i][j], 0, 0, 0);
+                            }
+                        }
+                    });
+                    __builtin_amdgcn_sched_barrier(0);
+                    // fragment k + 3 into the register just consumed; past the chunk's end the next
+                    // chunk's first three (its halo is certified by the barrier above)
+                    if constexpr (k + 3 < 3 * NFR) ds_rd<(16 * ((k + 3) / 3) + (k + 3) % 3) * 16>(F[r], a_cur);
+                    else ds_rd<(k + 3 - 3 * NFR) * 16>(F[r], a_nxt);
+                    __builtin_amdgcn_sched_barrier(0);
+                });
+                loadW(cn, I2{});
+                __builtin_amdgcn_sched_barrier(0);
+            }
+            // drain: the three fragment reads past the end and the reloaded weights are still in flight;
+            // they must land before the epilogue reuses their registers (tools/lds_hazards.py)
+            lgkm1<0>(F[0]);
+            lgkm1<0>(F[1]);
+            lgkm1<0>(F[2]);
+            asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");
+            epilogue(acc, 0, n0 + wave * 32 + 4 * lg);
+            return;
+        }
+    }
+
     f32x4v acc[NI][4];
 #pragma unroll
     for (int j = 0; j < 4; ++j) {                         // the bias seeds the accumulators
@@ -288,7 +525,6 @@ __global__ __launch_bounds__(256, RG == 3 ? 3 : 2) void conv3x3_v7(ConvBf16Args 
 
     // fragment addresses: activations (MFMA column operand) at halo row wm*WR + 16i + l16 + tap
     // shift, group l >> 4; weights (row operand) at channel wn*64 + 16j + l16, group l >> 4
-    const int l16 = lane & 15, lg = lane >> 4;
     const uint32_t a_lane = lds_addr(abuf) + lg * (HROWS * 16) + (wm * WR + l16) * 16;
     const uint32_t b_lane = lds_addr(bbuf) + lg * (BNT * 16) + (wn * 64 + l16) * 16;
     uint32_t mbits = 0;                                   // DENSE: board-edge bits of the lane's NI pixels
@@ -431,91 +667,7 @@ __global__ __launch_bounds__(256, RG == 3 ? 3 : 2) void conv3x3_v7(ConvBf16Args 
         main_loop(I0{});
     }
 
-    // epilogue, straight from the accumulators: lane holds channels 4*(l >> 4) + e of pixel l16
-    // of every 16 x 16 tile; residual join, ReLU, 16-bit + int8 split, streaming stores
-    const __amdgpu_buffer_rsrc_t rh = __builtin_amdgcn_make_buffer_rsrc((void*)p.Rhi, (short)0, 0x7fffffff, 0x00020000);
-    const __amdgpu_buffer_rsrc_t rq = __builtin_amdgcn_make_buffer_rsrc((void*)p.Rq, (short)0, 0x7fffffff, 0x00020000);
-    const int chl = n0 + wn * 64 + 4 * lg;                // first channel of the lane in tile j = 0
-    float vmax = 0.0f;                                    // fp16: the largest output (the range guard)
-    auto locate = [&](int i, int& b, int& pix) -> bool {  // fragment row i of the lane: board, pixel, live
-        const int q = wm * WR + i * 16 + l16;             // output grid row of the tile
-        if constexpr (DENSE) {
-            const int gq = tile * TM + q;
-            b = gq / HW;
-            pix = gq - b * HW;
-            return b < nboards;
-        } else {
-            const int y = q / WG, x = q - y * WG;
-            b = tile;
-            pix = y * HB + x;
-            return y < HB && x < HB;
-        }
-    };
-    // The residual join's loads go out EB fragment rows at a time (one memory round trip per burst,
-    // two per wave at NI = 8), not one round trip per row: each row's loads would otherwise wait
-    // behind the previous row's stores (the asm stores are memory barriers to the compiler), and a
-    // 2nd conv's epilogue was eight serial HBM round trips per wave (conv2 498 us vs conv1 423 us per
-    // C3 launch under PMC, profiles/r06_c3_fp16_pmc_calib.json).  <= 48 VGPRs per burst; the
-    // arithmetic and the stored values are unchanged.
-    constexpr int EB = NI <= 4 ? NI : NI % 4 == 0 ? 4 : NI % 3 == 0 ? 3 : NI % 2 == 0 ? 2 : 1;
-    static_assert(NI % EB == 0, "bursts");
-#pragma unroll
-    for (int i0 = 0; i0 < NI; i0 += EB) {
-    u32x2_t hv[EB][4];
-    uint32_t qv[EB][4];
-    if (p.Rhi) {
-#pragma unroll
-        for (int ii = 0; ii < EB; ++ii) {
-            int b, pix;
-            if (!locate(i0 + ii, b, pix)) continue;
-#pragma unroll
-            for (int j = 0; j < 4; ++j) {
-                const int ch = chl + j * 16;
-                const size_t e = (((size_t)b * GO + (ch >> 3)) * HW + pix) * 8 + (ch & 7);
-                hv[ii][j] = __builtin_amdgcn_raw_buffer_load_b64(rh, (int)(e * 2), 0, AZ_RES_AUX);
-                qv[ii][j] = __builtin_amdgcn_raw_buffer_load_b32(rq, (int)e, 0, AZ_RES_AUX);
-            }
-        }
-    }
-#pragma unroll
-    for (int ii = 0; ii < EB; ++ii) {
-        const int i = i0 + ii;
-        int b, pix;
-        if (!locate(i, b, pix)) continue;
-#pragma unroll
-        for (int j = 0; j < 4; ++j) {
-            const int ch = chl + j * 16;
-            const size_t e = (((size_t)b * GO + (ch >> 3)) * HW + pix) * 8 + (ch & 7);
-            float o[4] = {acc[i][j][0], acc[i][j][1], acc[i][j][2], acc[i][j][3]};
-            if (p.Rhi) {
-                uint16_t hh[4];
-                int8_t qq[4];
-                __builtin_memcpy(hh, &hv[ii][j], 8);
-                __builtin_memcpy(qq, &qv[ii][j], 4);
-#pragma unroll
-                for (int k = 0; k < 4; ++k) o[k] += H::join(hh[k], qq[k]);
-            }
-            uint16_t oh[4];
-            int8_t oq[4];
-#pragma unroll
-            for (int k = 0; k < 4; ++k) {
-                o[k] = __builtin_amdgcn_fmed3f(o[k], 0.0f, 3.0e38f);   // ReLU
-                if constexpr (MODE == 2) vmax = __builtin_fmaxf(vmax, o[k]);
-                if (p.Cq) H::split(o[k], oh[k], oq[k]);
-                else oh[k] = H::from_f(o[k]);
-            }
-            u32x2_t hs;
-            __builtin_memcpy(&hs, oh, 8);
-            asm volatile("global_store_dwordx2 %0, %1, off" AZ_V7_ST ::"v"(p.Chi + e), "v"(hs) : "memory");
-            if (p.Cq) {
-                uint32_t qs;
-                __builtin_memcpy(&qs, oq, 4);
-                asm volatile("global_store_dword %0, %1, off" AZ_V7_ST ::"v"(p.Cq + e), "v"(qs) : "memory");
-            }
-        }
-    }
-    }
-    if (MODE == 2 && !(vmax <= 65504.0f) && p.ovf) atomicOr(p.ovf, 1);   // fp16 overflow: the engine fails the forward
+    epilogue(acc, wm * WR, n0 + wn * 64 + 4 * lg);
 }
 
 // conv3x3_v7x3: the fp32-faithful trunk conv (AZ_PREC_BF16X3) on the v7 tile.
