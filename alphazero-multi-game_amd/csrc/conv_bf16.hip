@@ -1789,7 +1789,9 @@ int az_launch_pool_heads_g8(const uint16_t* hi, const int8_t* q, const float* Wt
 
 static int g_conv_flags = 4 | 0x200;   // bit 2: v6 (16x16x32) at 15x15; 0x200: v7 on 15x15 boards only
 // Variant bits for A/B measurement inside one process (tools/net_bench.py --flags): 0x2000 selects
-// conv3x3_v7's per-tap main loop on the SLIM tile (g8_choice below); no others defined now
+// conv3x3_v7's per-tap main loop on the SLIM tile (g8_choice below), 0x4000 keeps the row-streamed
+// loop's unpeeled tile tail (the last chunk reloads itself, the residual join reads global memory);
+// no others defined now
 // (a residual L2 prefetch during the main loop measured 0.6% slower and was removed; a cross-row
 // fragment prefetch and a mid-row barrier variant measured 1.5-2% slower)
 extern "C" int az_diag_set_conv_flags(int flags) { g_conv_flags = flags; return 0; }

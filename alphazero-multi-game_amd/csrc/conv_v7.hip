@@ -22,8 +22,11 @@
 //  * the SLIM 15x15 tile (the C3 trunk) runs a row-streamed main loop instead: the halo row pitch is
 //    one fragment, so each of 17 fragment rows x 3 column shifts is read from LDS once and multiplied
 //    into up to three output fragments; a wave owns the whole board x 32 channels and holds its tap
-//    weights of the chunk in registers, loaded straight from the packed weights.  Of the 72 KB only
-//    the halo double buffer (2 x 20 KB) is used, and there is one barrier per chunk (see the loop).
+//    weights of the chunk in registers, loaded straight from the packed weights.  There is one
+//    barrier per chunk (see the loop).  Its blocks own 80 KB: the halo double buffer (2 x 20 KB) and
+//    40 KB into which a 2nd conv's residual tile is fetched by LDS-DMA during the main loop (the last
+//    five of its 15 fragment rows go into the halo buffer the peeled last chunk leaves idle), so the
+//    epilogue's join reads LDS and the residual's HBM traffic is spread over the tile's MFMA time.
 //
 // Tile geometry (as v6): 15x15 boards use the padded grid (outputs on a 15x17 grid, one board per
 // 256-row tile, 225 of 256 rows live) or DENSE tiles; every other board uses DENSE tiles (256
@@ -115,6 +118,30 @@ __device__ unsigned g_v9_hw[V9_MAXB][2];
     } while (0)
 #else
 #define V9_STAMP(k) do { } while (0)
+#endif
+
+#ifdef AZ_V7_STAMPS
+// Diagnostic builds only (make EXTRA=-DAZ_V7_STAMPS OUT=build_stamps7): wave 0 of every block of the
+// selected conv3x3_v7 launch (ConvBf16Args::stamp == g_v7_sel) records s_memrealtime (100 MHz) at its
+// start, after the prologue barrier, at the main loop's end, when the first residual operands are in
+// registers (conv1: right away), after the last store issues and after all stores complete, plus
+// HW_ID / XCC_ID (tools/v7_stamps.py).  Row-streamed path only.
+constexpr int V7_MAXB = 8192, V7_NST = 6;
+__device__ int g_v7_sel = -1;
+__device__ unsigned long long g_v7_st[V7_MAXB][V7_NST];
+__device__ unsigned g_v7_hw[V7_MAXB][2];
+#define V7_STAMP(k)                                                                                 \
+    do {                                                                                            \
+        if (p.stamp == g_v7_sel && tid == 0 && blockIdx.x < V7_MAXB) {                              \
+            g_v7_st[blockIdx.x][k] = __builtin_amdgcn_s_memrealtime();                              \
+            if (k == 0) {                                                                           \
+                g_v7_hw[blockIdx.x][0] = __builtin_amdgcn_s_getreg((31 << 11) | 4);                 \
+                g_v7_hw[blockIdx.x][1] = __builtin_amdgcn_s_getreg((31 << 11) | 20);                \
+            }                                                                                       \
+        }                                                                                           \
+    } while (0)
+#else
+#define V7_STAMP(k) do { } while (0)
 #endif
 
 template <int OFF, typename F>
@@ -219,7 +246,12 @@ __global__ __launch_bounds__(256, RG == 3 ? 3 : 2) void conv3x3_v7(ConvBf16Args 
     constexpr int WR = TM / 2;                            // rows per wave
     constexpr int A_BUF = 4 * HROWS * 16;                 // one chunk: [4 groups][320 rows][16 B] = 20 KB
     constexpr int B_TAP = 4 * BNT * 16;                   // one tap: [4 groups][128 ch][16 B] = 8 KB
-    constexpr int LDS = 2 * A_BUF + RG * B_TAP;           // 72 KB (RG 4, TM 256); 48 KB (RG 3, TM 128)
+    constexpr bool ROWS = SLIM && WG == 16 && TM == 256 && RG == 4;   // the row-streamed main loop's geometry
+    constexpr int R_ROW = 4 * 1024;                       // ROWS: one fragment row of the block's residual tile (4 waves x 1 KB)
+    // 72 KB (RG 4, TM 256); 48 KB (RG 3, TM 128); ROWS 80 KB: behind the halo double buffer, rows 0..9
+    // of the residual tile's 16-bit plane (the per-tap loop's weight ring shares that area)
+    constexpr int LDS = ROWS ? 2 * A_BUF + 10 * R_ROW : 2 * A_BUF + RG * B_TAP;
+    static_assert(LDS >= 2 * A_BUF + RG * B_TAP && LDS <= 80 * 1024, "two blocks per CU");
     __shared__ __attribute__((aligned(16))) uint8_t lds[LDS];
 
     const int tid = threadIdx.x, lane = tid & 63;
@@ -231,6 +263,7 @@ __global__ __launch_bounds__(256, RG == 3 ? 3 : 2) void conv3x3_v7(ConvBf16Args 
     const int n0 = nb * BNT;
     const int nboards = p.m_limit ? *p.m_limit : p.M / HW;
     if (DENSE ? tile * TM >= nboards * HW : tile >= nboards) return;
+    V7_STAMP(0);
     const int C = p.C, GI = C / 8, GO = p.N / 8;
     const int NCH = C / 32, NS = 9 * NCH;
 
@@ -298,11 +331,17 @@ __global__ __launch_bounds__(256, RG == 3 ? 3 : 2) void conv3x3_v7(ConvBf16Args 
     // output grid row q0 x NJ 16-channel operands from channel chl - 4*lg: lane holds channels
     // chl + 16j + e of pixel l16 of every 16 x 16 tile; residual join, ReLU, 16-bit + int8 split,
     // streaming stores
-    auto epilogue = [&](auto& acc, const int q0, const int chl) {
+    // fetch(i, j, e, h, q): the residual of fragment row i, operand j (element index e): 16-bit plane h,
+    // int8 remainder q -- res_mem from global memory; the row-streamed loop has them on chip already
+    auto res_mem = [&](int, int, size_t e, u32x2_t& h, uint32_t& q) {
+        const __amdgpu_buffer_rsrc_t rh = __builtin_amdgcn_make_buffer_rsrc((void*)p.Rhi, (short)0, 0x7fffffff, 0x00020000);
+        const __amdgpu_buffer_rsrc_t rq = __builtin_amdgcn_make_buffer_rsrc((void*)p.Rq, (short)0, 0x7fffffff, 0x00020000);
+        h = __builtin_amdgcn_raw_buffer_load_b64(rh, (int)(e * 2), 0, AZ_RES_AUX);
+        q = __builtin_amdgcn_raw_buffer_load_b32(rq, (int)e, 0, AZ_RES_AUX);
+    };
+    auto epilogue = [&](auto& acc, const int q0, const int chl, auto&& fetch) {
     typedef typename std::remove_reference<decltype(acc)>::type AccT;
     constexpr int NIE = std::extent<AccT, 0>::value, NJ = std::extent<AccT, 1>::value;
-    const __amdgpu_buffer_rsrc_t rh = __builtin_amdgcn_make_buffer_rsrc((void*)p.Rhi, (short)0, 0x7fffffff, 0x00020000);
-    const __amdgpu_buffer_rsrc_t rq = __builtin_amdgcn_make_buffer_rsrc((void*)p.Rq, (short)0, 0x7fffffff, 0x00020000);
     float vmax = 0.0f;                                    // fp16: the largest output (the range guard)
     auto locate = [&](int i, int& b, int& pix) -> bool {  // fragment row i of the lane: board, pixel, live
         const int q = q0 + i * 16 + l16;                  // output grid row of the tile
@@ -339,11 +378,16 @@ __global__ __launch_bounds__(256, RG == 3 ? 3 : 2) void conv3x3_v7(ConvBf16Args 
             for (int j = 0; j < NJ; ++j) {
                 const int ch = chl + j * 16;
                 const size_t e = (((size_t)b * GO + (ch >> 3)) * HW + pix) * 8 + (ch & 7);
-                hv[ii][j] = __builtin_amdgcn_raw_buffer_load_b64(rh, (int)(e * 2), 0, AZ_RES_AUX);
-                qv[ii][j] = __builtin_amdgcn_raw_buffer_load_b32(rq, (int)e, 0, AZ_RES_AUX);
+                fetch(i0 + ii, j, e, hv[ii][j], qv[ii][j]);
             }
         }
     }
+#ifdef AZ_V7_STAMPS
+    if (i0 == 0) {                                        // the first burst's residual operands are in registers
+        asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");
+        V7_STAMP(3);
+    }
+#endif
 #pragma unroll
     for (int ii = 0; ii < EB; ++ii) {
         const int i = i0 + ii;
@@ -402,9 +446,20 @@ __global__ __launch_bounds__(256, RG == 3 ? 3 : 2) void conv3x3_v7(ConvBf16Args 
     //  * every accumulator still receives its nine taps in the order t = 3*dy + dx (f ascending is dy
     //    ascending for a fixed output fragment), chunk after chunk, seeded by the bias: the result is
     //    bitwise that of the per-tap loop and of conv3x3_v6.
-    // vmcnt counts the halo's DMA pieces and the weight loads together in issue order; the budgets
-    // below are compile-time constants (past the last chunk both are harmless reloads).
-    constexpr bool ROWS = SLIM && WG == 16 && TM == 256 && RG == 4;
+    //  * the last chunk is peeled: it has no next halo and no next weights to fetch and no barrier.
+    //    A 2nd conv's residual tile arrives during the main loop instead of in the epilogue, where the
+    //    co-resident blocks' joins would all ask HBM at once.  The wave's part of the 16-bit plane is
+    //    15 fragment rows x 4 eight-channel groups; one row is one 1-KB LDS-DMA piece (lane = group x
+    //    16 grid pixels, the dead 16th column re-reads pixel 14).  Rows 0..9 go behind the halo
+    //    buffers, a few per chunk from the first chunk on (up to four, at dx == 1 of f = 0..3, so that
+    //    they precede the chunk's last halo piece in the vmcnt order); rows 10..14 go into the halo
+    //    buffer the last chunk leaves idle, in the slots where an unpeeled last chunk would reload its
+    //    own halo.  The 30 int8-remainder loads of the wave go out in the last chunk too, into the
+    //    registers of the dead tap rows.  Every piece is read back only by the wave that fetched it,
+    //    after its own vmcnt(0) behind the loop: no barrier.  Conv flag 0x4000 keeps the unpeeled
+    //    tile tail (the last chunk reloads itself, the join reads global memory in bursts of three rows).
+    // vmcnt counts the halo's DMA pieces, the residual pieces and the weight loads together in issue
+    // order; the budget before the chunk barrier is a compile-time constant (see there).
     if constexpr (ROWS) {
         if (!(p.flags & 0x2000)) {
             constexpr int NF = GM::NFRAG, NFR = NF + 2;   // 15 output fragments, 17 fragment rows of the halo
@@ -451,36 +506,112 @@ __global__ __launch_bounds__(256, RG == 3 ? 3 : 2) void conv3x3_v7(ConvBf16Args 
             __builtin_amdgcn_sched_barrier(0);
             wait_vmc<18>();                               // the halo landed; the weights may fly
             __builtin_amdgcn_s_barrier();
+            V7_STAMP(1);
             __builtin_amdgcn_sched_barrier(0);
             ds_rd<0 * 16>(F[0], a_lane);
             ds_rd<1 * 16>(F[1], a_lane);
             ds_rd<2 * 16>(F[2], a_lane);
 
-            for (int c = 0; c < NCH; ++c) {
-                const int cn = c + 1 < NCH ? c + 1 : c;   // the last chunk reloads itself
+            // The residual tile: nothing of it on a conv without residual or under flag 0x4000.  Row r of
+            // the wave's 15: rows 0..RR0-1 behind the halo buffers, the rest in halo buffer NCH & 1,
+            // which the last chunk (reading buffer (NCH - 1) & 1) leaves idle; [row][wave][1 KB].
+            constexpr int RR0 = 10;
+            static_assert(2 * A_BUF + RR0 * R_ROW <= LDS && (NF - RR0) * R_ROW <= A_BUF && NF - RR0 <= NRB, "residual images");
+            const bool tail_old = (p.flags & 0x4000) != 0;
+            const bool resid = p.Rhi && !tail_old;
+            const __amdgpu_buffer_rsrc_t rsR = __builtin_amdgcn_make_buffer_rsrc((void*)p.Rhi, (short)0, 0x7fffffff, 0x00020000);
+            uint8_t* const r_lo = lds + 2 * A_BUF + wave * 1024;
+            uint8_t* const r_hi = abuf + (NCH & 1) * A_BUF + wave * 1024;
+            auto issueR = [&](int r) {                    // r wave-uniform
+                int ln = lane;
+                asm volatile("" : "+v"(ln));              // recompute here, do not hoist
+                const uint32_t vo = (uint32_t)(((ln >> 4) * HW + min(ln & 15, HB - 1)) * 16);
+                const int so = __builtin_amdgcn_readfirstlane((int)((((size_t)tile * GO + (n0 + wave * 32) / 8) * HW + r * HB) * 16));
+                uint8_t* dst = r < RR0 ? r_lo + r * R_ROW : r_hi + (r - RR0) * R_ROW;
+                __builtin_amdgcn_raw_ptr_buffer_load_lds(rsR, (lds_void_t*)dst, 16, (int)vo, so, 0, AZ_RES_AUX);
+            };
+            // rows 0..RR0-1 spread over the chunks before the last: `per` of them per chunk (at most the
+            // four slots a chunk has); what few chunks (C < 128) leave over goes out first in the last chunk
+            int rnext = 0;
+            const int per = resid ? min(4, (RR0 + NCH - 2) / (NCH - 1)) : 0;
+            // the int8 remainder of fragment row i (the dead 16th column re-reads pixel 14)
+            uint32_t QV[NF][2];
+            auto loadQ = [&](int i) {
+                const __amdgpu_buffer_rsrc_t rq = __builtin_amdgcn_make_buffer_rsrc((void*)p.Rq, (short)0, 0x7fffffff, 0x00020000);
+                const uint32_t qo = (uint32_t)((((n0 + wave * 32) / 8 + (lg >> 1)) * HW + min(l16, HB - 1)) * 8 + 4 * (lg & 1));
+                const int so = __builtin_amdgcn_readfirstlane((int)(((size_t)tile * GO * HW + i * HB) * 8));
+#pragma unroll
+                for (int j = 0; j < 2; ++j)
+                    QV[i][j] = __builtin_amdgcn_raw_buffer_load_b32(rq, (int)(qo + j * (2 * HW * 8)), so, AZ_RES_AUX);
+            };
+            auto res_lds = [&](int i, int j, size_t, u32x2_t& h, uint32_t& q) {
+                const uint8_t* src = (i < RR0 ? r_lo + i * R_ROW : r_hi + (i - RR0) * R_ROW) + (2 * j + (lg >> 1)) * 256 + l16 * 16 + (lg & 1) * 8;
+                h = *reinterpret_cast<const u32x2_t*>(src);
+                q = QV[i][j];
+            };
+
+            // one chunk; lastc: the peeled last chunk
+            auto chunk = [&](const int c, auto lastc) {
+                constexpr bool LASTC = decltype(lastc)::value;
+                const int cn = c + 1 < NCH ? c + 1 : c;   // flag 0x4000: the last chunk reloads itself
                 const uint32_t a_cur = a_lane + (c & 1) * A_BUF, a_nxt = a_lane + ((c + 1) & 1) * A_BUF;
+                if constexpr (LASTC) {
+                    if (resid)
+                        for (; rnext < RR0; ++rnext) issueR(rnext);
+                }
                 static_for<0, 3 * NFR>([&](auto kc) {
                     constexpr int k = decltype(kc)::value, f = k / 3, dx = k % 3, r = k % 3;
                     constexpr int LAST = 3 * (NFR - 1);   // first step of the last fragment row
                     if constexpr (k == LAST) {
                         // every fragment read of this chunk has landed (none is issued after this point),
                         // and so have this wave's pieces of the next halo: the six W(0,.) loads issued at
-                        // f = 15 are the only younger vector-memory operations.  Past the barrier every
-                        // wave is done with this chunk's halo buffer, which the next chunk's DMA overwrites,
-                        // and the next chunk's halo is complete.
+                        // f = 15 are the only younger vector-memory operations -- the halo's last piece
+                        // goes out at k = 12, the chunk's residual pieces before it (k = 1, 4, 7, 10), so
+                        // vmcnt(6) certifies both whether or not this chunk fetched residual rows.  Past
+                        // the barrier every wave is done with this chunk's halo buffer, which the next
+                        // chunk's DMA overwrites, and the next chunk's halo is complete.  The last chunk
+                        // has nothing to certify and no buffer to hand over: no barrier.
                         lgkm1<0>(F[0]);
                         lgkm1<0>(F[1]);
                         lgkm1<0>(F[2]);
-                        wait_vmc<6>();
-                        __builtin_amdgcn_s_barrier();
+                        if constexpr (!LASTC) {
+                            wait_vmc<6>();
+                            __builtin_amdgcn_s_barrier();
+                        }
                     } else {
                         lgkm1<2>(F[r]);                   // fragments k + 1 and k + 2 stay in flight
                     }
                     __builtin_amdgcn_sched_barrier(0);
-                    // DMA: piece f of the next chunk's halo at f = 0..4; the next chunk's tap rows as they die
-                    if constexpr (dx == 0 && f < NRB) issueA(f, cn, (c + 1) & 1);
-                    if constexpr (k == 3 * NF) loadW(cn, I0{});
-                    if constexpr (k == LAST) loadW(cn, I1{});
+                    if constexpr (!LASTC) {
+                        // DMA: piece f of the next chunk's halo at f = 0..4, a residual row behind each of the
+                        // first four; the next chunk's tap rows as they die
+                        if constexpr (dx == 0 && f < NRB) issueA(f, cn, (c + 1) & 1);
+                        if constexpr (dx == 1 && f < 4) {
+                            if (f < per && rnext < RR0) {
+                                issueR(rnext);
+                                ++rnext;
+                            }
+                        }
+                        if constexpr (k == 3 * NF) loadW(cn, I0{});
+                        if constexpr (k == LAST) loadW(cn, I1{});
+                    } else {
+                        // residual rows 10..14 in the halo's slots; the remainder plane where the tap rows die
+                        if constexpr (dx == 0 && f < NF - RR0) {
+                            if (resid) issueR(RR0 + f);
+                        }
+                        if constexpr (k == 3 * NF) {
+                            if (resid) {
+#pragma unroll
+                                for (int i = 0; i < 12; ++i) loadQ(i);
+                            }
+                        }
+                        if constexpr (k == LAST) {
+                            if (resid) {
+#pragma unroll
+                                for (int i = 12; i < NF; ++i) loadQ(i);
+                            }
+                        }
+                    }
                     __builtin_amdgcn_sched_barrier(0);
                     static_for<0, 3>([&](auto dyc) {
                         constexpr int dy = decltype(dyc)::value, i = f - dy;
@@ -498,19 +629,32 @@ __global__ __launch_bounds__(256, RG == 3 ? 3 : 2) void conv3x3_v7(ConvBf16Args 
                     // fragment k + 3 into the register just consumed; past the chunk's end the next
                     // chunk's first three (its halo is certified by the barrier above)
                     if constexpr (k + 3 < 3 * NFR) ds_rd<(16 * ((k + 3) / 3) + (k + 3) % 3) * 16>(F[r], a_cur);
-                    else ds_rd<(k + 3 - 3 * NFR) * 16>(F[r], a_nxt);
+                    else if constexpr (!LASTC) ds_rd<(k + 3 - 3 * NFR) * 16>(F[r], a_nxt);
                     __builtin_amdgcn_sched_barrier(0);
                 });
-                loadW(cn, I2{});
-                __builtin_amdgcn_sched_barrier(0);
-            }
-            // drain: the three fragment reads past the end and the reloaded weights are still in flight;
-            // they must land before the epilogue reuses their registers (tools/lds_hazards.py)
+                if constexpr (!LASTC) {
+                    loadW(cn, I2{});
+                    __builtin_amdgcn_sched_barrier(0);
+                }
+            };
+            const int nloop = tail_old ? NCH : NCH - 1;
+            for (int c = 0; c < nloop; ++c) chunk(c, std::false_type{});
+            if (!tail_old) chunk(NCH - 1, std::true_type{});
+            V7_STAMP(2);
+            // drain: under flag 0x4000 the three fragment reads past the end and the reloaded weights are
+            // still in flight; they must land before the epilogue reuses their registers
+            // (tools/lds_hazards.py).  The wave's residual pieces and remainder loads land here too.
             lgkm1<0>(F[0]);
             lgkm1<0>(F[1]);
             lgkm1<0>(F[2]);
             asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");
-            epilogue(acc, 0, n0 + wave * 32 + 4 * lg);
+            if (tail_old) epilogue(acc, 0, n0 + wave * 32 + 4 * lg, res_mem);
+            else epilogue(acc, 0, n0 + wave * 32 + 4 * lg, res_lds);
+#ifdef AZ_V7_STAMPS
+            V7_STAMP(4);
+            asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+            V7_STAMP(5);
+#endif
             return;
         }
     }
@@ -667,7 +811,7 @@ __global__ __launch_bounds__(256, RG == 3 ? 3 : 2) void conv3x3_v7(ConvBf16Args 
         main_loop(I0{});
     }
 
-    epilogue(acc, wm * WR, n0 + wn * 64 + 4 * lg);
+    epilogue(acc, wm * WR, n0 + wn * 64 + 4 * lg, res_mem);
 }
 
 // conv3x3_v7x3: the fp32-faithful trunk conv (AZ_PREC_BF16X3) on the v7 tile.
@@ -1392,6 +1536,27 @@ extern "C" int az_diag_v9_stamps(int sel, unsigned long long* st, unsigned* hw, 
         if (hipDeviceSynchronize() != hipSuccess) return -2;
         if (hipMemcpyFromSymbol(st, HIP_SYMBOL(g_v9_st), (size_t)n * 5 * 8) != hipSuccess) return -2;
         if (hw && hipMemcpyFromSymbol(hw, HIP_SYMBOL(g_v9_hw), (size_t)n * 2 * 4) != hipSuccess) return -2;
+    }
+    return 0;
+#else
+    (void)sel; (void)st; (void)hw; (void)n;
+    return -1;
+#endif
+}
+
+// diagnostic: select the stamped conv3x3_v7 launch / read its stamps (AZ_V7_STAMPS builds; else -1)
+extern "C" int az_diag_v7_stamps(int sel, unsigned long long* st, unsigned* hw, int n) {
+#ifdef AZ_V7_STAMPS
+    if (sel >= -1) {
+        if (hipMemcpyToSymbol(HIP_SYMBOL(g_v7_sel), &sel, sizeof(int)) != hipSuccess) return -2;
+        static unsigned long long zero[V7_MAXB][V7_NST];
+        if (hipMemcpyToSymbol(HIP_SYMBOL(g_v7_st), zero, sizeof(zero)) != hipSuccess) return -2;
+    }
+    if (st && n > 0) {
+        n = n < V7_MAXB ? n : V7_MAXB;
+        if (hipDeviceSynchronize() != hipSuccess) return -2;
+        if (hipMemcpyFromSymbol(st, HIP_SYMBOL(g_v7_st), (size_t)n * V7_NST * 8) != hipSuccess) return -2;
+        if (hw && hipMemcpyFromSymbol(hw, HIP_SYMBOL(g_v7_hw), (size_t)n * 2 * 4) != hipSuccess) return -2;
     }
     return 0;
 #else
