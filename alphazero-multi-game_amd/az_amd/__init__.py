@@ -18,7 +18,7 @@ from dataclasses import dataclass, field
 
 import numpy as np
 
-from ._lib import (AZ_GO_RULES_SET, AZ_EVAL_CALLBACK, AZ_EVAL_HASH, AZ_EVAL_NET, AZ_EVAL_RANDOM, AZ_EVAL_UNIFORM, EVAL_FN, AZ_PREC_BF16, AZ_PREC_BF16X3, AZ_PREC_F16X3, AZ_PREC_F32, AZ_PREC_FP16, AzError,
+from ._lib import (AZ_GO_RULES_SET, AZ_SEL_PROGRESSIVE_BIAS, AZ_SEL_PUCT, AZ_SEL_RAVE, AZ_SEL_UCB, SearchOpts, AZ_EVAL_CALLBACK, AZ_EVAL_HASH, AZ_EVAL_NET, AZ_EVAL_RANDOM, AZ_EVAL_UNIFORM, EVAL_FN, AZ_PREC_BF16, AZ_PREC_BF16X3, AZ_PREC_F16X3, AZ_PREC_F32, AZ_PREC_FP16, AzError,
                    ARENA_SINK, ArenaCfg, ArenaSummary, GAME_SINK, PROGRESS_FN, MoveRec as _lib_MoveRec, NetDesc, SearchCfg, SelfPlayCfg, check, lib)
 
 __all__ = ["Engine", "HipNeuralNetwork", "ParallelMCTS", "SelfPlayManager", "Arena", "ArenaGameRecord", "EloRating", "GameRecord", "MoveData", "AzError",
@@ -211,6 +211,33 @@ def _go_rules_fields(game, komi, chinese, superko):
     return AZ_GO_RULES_SET, komi, int(bool(chinese)), int(bool(superko))
 
 
+SEARCH_OPT_DEFAULTS = dict(selection=AZ_SEL_PUCT, max_search_depth=1000, use_td=False, td_lambda=0.8, use_widening=False,
+                           widening_min_visits=10, widening_base=2.0, widening_exponent=0.5)
+
+
+def _search_opts_struct(opts):
+    """az_search_opts from keyword arguments named as SEARCH_OPT_DEFAULTS (MCTSConfig's selectionStrategy,
+    maxSearchDepth, useTemporalDifference, tdLambda, useProgressiveWidening, minVisitsForWidening,
+    progressiveWideningBase / Exponent); the ones not named take their defaults."""
+    unknown = set(opts) - set(SEARCH_OPT_DEFAULTS)
+    if unknown:
+        raise TypeError(f"unknown search options {sorted(unknown)}")
+    o = dict(SEARCH_OPT_DEFAULTS, **opts)
+    return SearchOpts(int(o["selection"]), int(o["max_search_depth"]), int(bool(o["use_td"])), float(o["td_lambda"]),
+                      int(bool(o["use_widening"])), int(o["widening_min_visits"]), float(o["widening_base"]),
+                      float(o["widening_exponent"]))
+
+
+def widening_table(base, exponent, n_actions):
+    """The progressive-widening counts by visit count the device reads (az_search_widening_table;
+    host only): the whole table as an int32 array."""
+    n = ctypes.c_int()
+    check(lib().az_search_widening_table(base, exponent, n_actions, None, 0, ctypes.byref(n)))
+    out = np.zeros(n.value, np.int32)
+    check(lib().az_search_widening_table(base, exponent, n_actions, _ip(out), out.size, ctypes.byref(n)))
+    return out
+
+
 class ParallelMCTS:
     """G independent ParallelMCTS trees (Mode S semantics, setDeterministicMode) on one device."""
 
@@ -218,10 +245,13 @@ class ParallelMCTS:
                  virtual_loss=3, evaluator=AZ_EVAL_HASH, net=None, eval_seed=7, zobrist_seed=12345, noise_seed=42,
                  noise_seed_stride=0, use_dirichlet_each_search=False, dirichlet_alpha=0.03, dirichlet_eps=0.25,
                  tt_log2=20, node_capacity=0, prior_ring=0, game=0, callback=None, go_komi=7.5, go_chinese_rules=True,
-                 go_superko=True):
+                 go_superko=True, **search_opts):
         """game: AZ_GAME_GOMOKU (0) or AZ_GAME_GO (1) -- GoState(bs 9/13/19, go_komi, go_chinese_rules,
         go_superko), fixed for the handle's life; Go actions are -1 (pass) .. bs*bs-1 and finished games
         report AZ_ACTION_NONE.
+        search_opts: selection (AZ_SEL_*), max_search_depth, use_td, td_lambda, use_widening,
+        widening_min_visits, widening_base, widening_exponent (SEARCH_OPT_DEFAULTS), put in force right
+        after creation (az_search_set_options); setSearchOptions changes them on the live handle.
         evaluator=AZ_EVAL_CALLBACK: callback(games [n], moves: per leaf the moves from the empty board,
         planes [n][C][bs][bs]) -> (policy [n][NA] as NeuralNetwork::predict returns it, value [n])."""
         self.G = n_games
@@ -234,9 +264,16 @@ class ParallelMCTS:
                         dirichlet_alpha, dirichlet_eps, tt_log2, node_capacity, prior_ring, game,
                         *_go_rules_fields(game, go_komi, go_chinese_rules, go_superko))
         self.cfg = cfg
+        opts = _search_opts_struct(search_opts)
         h = ctypes.c_void_p()
         check(lib().az_search_create(engine.h, net.h if net is not None else None, ctypes.byref(cfg), ctypes.byref(h)))
         self.h = h
+        if search_opts:
+            try:
+                check(lib().az_search_set_options(h, ctypes.byref(opts)))
+            except AzError:
+                self.close()
+                raise
         self.engine, self.net = engine, net
         self._cb = None
         if evaluator == AZ_EVAL_CALLBACK:
@@ -382,6 +419,20 @@ class ParallelMCTS:
         check(lib().az_search_go_rules(self.h, ctypes.byref(k), ctypes.byref(c), ctypes.byref(sk)))
         return k.value, bool(c.value), bool(sk.value)
 
+    def searchOptions(self):
+        """The search options the handle plays (az_search_options), keyed as SEARCH_OPT_DEFAULTS."""
+        o = SearchOpts()
+        check(lib().az_search_options(self.h, ctypes.byref(o)))
+        return dict(selection=o.selection, max_search_depth=o.max_search_depth, use_td=bool(o.use_td), td_lambda=o.td_lambda,
+                    use_widening=bool(o.use_widening), widening_min_visits=o.widening_min_visits,
+                    widening_base=o.widening_base, widening_exponent=o.widening_exponent)
+
+    def setSearchOptions(self, **search_opts):
+        """setSelectionStrategy / setConfig on the live handle, trees kept (az_search_set_options): the
+        options named change, the others stay as they are."""
+        opts = _search_opts_struct(dict(self.searchOptions(), **search_opts))
+        check(lib().az_search_set_options(self.h, ctypes.byref(opts)))
+
     def rootNode(self, game):
         N = ctypes.c_int()
         VL = ctypes.c_int()
@@ -500,6 +551,8 @@ class SelfPlayManager:
 
     def __init__(self, engine, net=None, numGames=1, numSimulations=800, board_size=15, evaluator=None, **mcts_kw):
         ev = evaluator if evaluator is not None else (AZ_EVAL_NET if net is not None else AZ_EVAL_HASH)
+        if mcts_kw.get("selection") == AZ_SEL_UCB:      # playSingleGame turns UCB into PUCT (self_play_manager.cpp:180-181)
+            mcts_kw = dict(mcts_kw, selection=AZ_SEL_PUCT)
         self.mcts = ParallelMCTS(engine, n_games=numGames, board_size=board_size, num_simulations=numSimulations,
                                  evaluator=ev, net=net, **mcts_kw)
         self.numGames = numGames
@@ -620,12 +673,14 @@ class Arena:
     def __init__(self, engine, net_a, net_b, tables, board_size=15, num_simulations=800, swap_colors=False,
                  temperature=0.1, sample_moves=0, noise_alpha=0.03, noise_eps=0.0, game=0, c_puct=1.5,
                  fpu_reduction=0.0, virtual_loss=3, zobrist_seed=12345, noise_seed=42, noise_seed_stride=1, tt_log2=20,
-                 node_capacity=0, prior_ring=0, go_komi=7.5, go_chinese_rules=True, go_superko=True):
+                 node_capacity=0, prior_ring=0, go_komi=7.5, go_chinese_rules=True, go_superko=True, **search_opts):
+        """search_opts: the search options of ParallelMCTS (SEARCH_OPT_DEFAULTS), played by both nets' trees."""
         self.tables, self.engine, self.nets = int(tables), engine, (net_a, net_b)
         self.cfg = SearchCfg(self.tables, board_size, num_simulations, c_puct, fpu_reduction, virtual_loss, AZ_EVAL_NET,
                              7, zobrist_seed, noise_seed, noise_seed_stride, 0, noise_alpha, noise_eps, tt_log2,
                              node_capacity, prior_ring, game,
                              *_go_rules_fields(game, go_komi, go_chinese_rules, go_superko))
+        opts = _search_opts_struct(search_opts)
         self.acfg = ArenaCfg(int(bool(swap_colors)), temperature, int(sample_moves), noise_alpha, noise_eps)
         h = ctypes.c_void_p()
         check(lib().az_arena_create(engine.h, net_a.h, net_b.h, ctypes.byref(self.cfg), ctypes.byref(self.acfg),
@@ -640,6 +695,12 @@ class Arena:
         m.engine, m.net, m._cb, m._borrowed, m.cfg = engine, net_a, None, True, self.cfg
         self.search = m
         self.progressCallback = None
+        if search_opts:                                       # both nets' trees: every slot of the arena's handle
+            try:
+                check(lib().az_search_set_options(m.h, ctypes.byref(opts)))
+            except AzError:
+                self.close()
+                raise
 
     def step(self):
         """One ply on every live table; returns the moves played."""

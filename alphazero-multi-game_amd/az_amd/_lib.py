@@ -39,7 +39,14 @@ class SearchCfg(ctypes.Structure):
                 ("go_rules", c_int), ("go_komi", c_float), ("go_chinese_rules", c_int), ("go_superko", c_int)]
 
 
+class SearchOpts(ctypes.Structure):
+    _fields_ = [("selection", c_int), ("max_search_depth", c_int), ("use_td", c_int), ("td_lambda", c_float),
+                ("use_widening", c_int), ("widening_min_visits", c_int), ("widening_base", c_float),
+                ("widening_exponent", c_float)]
+
+
 AZ_GO_RULES_SET = 1
+AZ_SEL_UCB, AZ_SEL_PUCT, AZ_SEL_PROGRESSIVE_BIAS, AZ_SEL_RAVE = 0, 1, 2, 3
 
 
 class SelfPlayCfg(ctypes.Structure):
@@ -123,6 +130,10 @@ EXPORTS = {
     "az_search_set_evaluator": (c_int, [vp, EVAL_FN, vp]),
     "az_search_set_params": (c_int, [vp, P(SearchCfg)]),
     "az_search_go_rules": (c_int, [vp, P(c_float), P(c_int), P(c_int)]),
+    "az_search_set_options": (c_int, [vp, P(SearchOpts)]),
+    "az_search_options": (c_int, [vp, P(SearchOpts)]),
+    "az_search_widening_table": (c_int, [c_float, c_float, c_int, P(c_int), c_int, P(c_int)]),
+    "az_diag_set_widening_cap": (c_int, [c_int]),
     "az_search_root_node": (c_int, [vp, c_int, P(c_int), P(c_int), P(c_float)]),
     "az_search_counters": (c_int, [vp, c_int, P(c_int64)]),
     "az_search_profile": (c_int, [vp, c_int]),

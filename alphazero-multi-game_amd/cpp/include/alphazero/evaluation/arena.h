@@ -9,6 +9,7 @@
 #include <vector>
 
 #include "alphazero/core/igamestate.h"
+#include "alphazero/mcts/parallel_mcts.h"
 #include "alphazero/nn/hip_neural_network.h"
 #include "alphazero/selfplay/game_record.h"
 #include "az_engine.h"
@@ -45,6 +46,9 @@ struct ArenaConfig {
     float noiseAlpha = 0.03f, noiseEpsilon = 0.0f;   // root noise of the mover (evaluate.py adds none)
     uint32_t seed = 42;          // the games' generators: seed + stream id
     int ttLog2 = 20;             // TranspositionTable(1048576, 1024), evaluate.py:336-337
+    // both trees' search options: only selectionStrategy, maxSearchDepth, the TD and the widening fields
+    // are read (mcts::searchOptions)
+    mcts::MCTSConfig searchOptions;
 };
 
 struct ArenaGame {

@@ -5,6 +5,9 @@
 // as the reference does: the deterministic rules (forced by setDeterministicMode and by
 // SelfPlayManager) or libstdc++ draws on rng_ (parallel_mcts.cpp:987-1047).  numThreads / batch
 // settings are accepted and ignored (the device runs one simulation per game per step, Mode S).
+// selectionStrategy, maxSearchDepth, useTemporalDifference / tdLambda and the progressive-widening
+// fields of MCTSConfig go down to the device search (az_search_set_options) at creation and through
+// the setters, which keep the tree.
 #pragma once
 #include <atomic>
 #include <functional>
@@ -105,7 +108,7 @@ class ParallelMCTS {
     void setVirtualLoss(int v);
     void setNeuralNetwork(nn::NeuralNetwork* nn);
     void setTranspositionTable(TranspositionTable* tt);
-    void setSelectionStrategy(MCTSNodeSelection s) { config_.selectionStrategy = s; }
+    void setSelectionStrategy(MCTSNodeSelection s);
     void setConfig(const MCTSConfig& config);
     void enableBatchedMCTS(bool enable) { config_.useBatchedMCTS = enable; }
     void setBatchSize(int b) { config_.batchSize = b; }

@@ -42,6 +42,11 @@ az_search_cfg makeSearchConfig(const MCTSConfig& config, const core::IGameState&
                                const TranspositionTable* tt, int nGames);
 // Both configurations name the same Go rules (komi, scoring, ko rule), which a handle keeps for life.
 bool sameGoRules(const az_search_cfg& a, const az_search_cfg& b);
+// config's search options (selectionStrategy, maxSearchDepth, useTemporalDifference / tdLambda,
+// useProgressiveWidening / minVisitsForWidening / progressiveWideningBase / Exponent) as the device takes
+// them (az_search_set_options); and whether two sets are the same.
+az_search_opts searchOptions(const MCTSConfig& config);
+bool sameSearchOptions(const az_search_opts& a, const az_search_opts& b);
 
 class SearchGroup {
  public:
@@ -70,10 +75,12 @@ class SearchGroup {
     void search(int slot);                       // blocks until a device search covering `slot` has finished
     az_search* handle() const { return s_; }
     const az_search_cfg& deviceConfig() const { return cfg_; }
+    const az_search_opts& deviceOptions() const { return opts_; }   // every member's search options
     nn::NeuralNetwork* network() const { return nn_; }
 
     nn::NeuralNetwork* nn_;
     az_search_cfg cfg_{};
+    az_search_opts opts_{};
     int capacity_;
     az_search* s_ = nullptr;
     mutable std::mutex mu_;

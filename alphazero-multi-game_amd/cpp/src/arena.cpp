@@ -91,6 +91,13 @@ Arena::Arena(nn::HipNeuralNetwork& a, nn::HipNeuralNetwork& b, const ArenaConfig
     ac.noise_alpha = config.noiseAlpha;
     ac.noise_eps = config.noiseEpsilon;
     check(az_arena_create(a.engine(), a.handle(), b.handle(), &sc, &ac, &arena_), "az_arena_create");
+    const az_search_opts so = mcts::searchOptions(config.searchOptions);   // both nets' trees: every slot
+    if (az_search_set_options(az_arena_search(arena_), &so) != 0) {
+        const std::string msg = az_last_error();
+        az_arena_destroy(arena_);
+        arena_ = nullptr;
+        throw std::runtime_error("az_search_set_options: " + msg);
+    }
 }
 
 Arena::~Arena() { az_arena_destroy(arena_); }

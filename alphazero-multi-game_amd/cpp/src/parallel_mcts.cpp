@@ -115,6 +115,16 @@ ParallelMCTS::ParallelMCTS(const core::IGameState& root, SearchGroup& group)
     config_.dirichletAlpha = g.dirichlet_alpha;
     config_.dirichletEpsilon = g.dirichlet_eps;
     config_.transpositionTableSize = 1 << g.tt_log2;
+    // the group's search options are every member's
+    const az_search_opts& go = group.deviceOptions();
+    config_.selectionStrategy = static_cast<MCTSNodeSelection>(go.selection);
+    config_.maxSearchDepth = go.max_search_depth;
+    config_.useTemporalDifference = go.use_td != 0;
+    config_.tdLambda = go.td_lambda;
+    config_.useProgressiveWidening = go.use_widening != 0;
+    config_.minVisitsForWidening = go.widening_min_visits;
+    config_.progressiveWideningBase = go.widening_base;
+    config_.progressiveWideningExponent = go.widening_exponent;
     if (root_->getBoardSize() != g.board_size || (root_->getGameType() == core::GameType::GO) != (g.game == AZ_GAME_GO))
         throw std::invalid_argument("ParallelMCTS: the root's game does not match the group's");
     if (!sameGoRules(makeSearchConfig(config_, *root_, nn_, nullptr, 1), g))
@@ -164,6 +174,26 @@ az_search_cfg makeSearchConfig(const MCTSConfig& config, const core::IGameState&
     return c;
 }
 
+az_search_opts searchOptions(const MCTSConfig& config) {
+    az_search_opts c{};
+    c.selection = static_cast<int>(config.selectionStrategy);   // the reference enum's order
+    c.max_search_depth = config.maxSearchDepth;
+    c.use_td = config.useTemporalDifference ? 1 : 0;
+    c.td_lambda = config.tdLambda;
+    c.use_widening = config.useProgressiveWidening ? 1 : 0;
+    c.widening_min_visits = config.minVisitsForWidening;
+    c.widening_base = config.progressiveWideningBase;
+    c.widening_exponent = config.progressiveWideningExponent;
+    return c;
+}
+
+bool sameSearchOptions(const az_search_opts& a, const az_search_opts& b) {
+    return a.selection == b.selection && a.max_search_depth == b.max_search_depth &&
+           a.use_td == b.use_td && a.td_lambda == b.td_lambda && a.use_widening == b.use_widening &&
+           a.widening_min_visits == b.widening_min_visits && a.widening_base == b.widening_base &&
+           a.widening_exponent == b.widening_exponent;
+}
+
 bool sameGoRules(const az_search_cfg& a, const az_search_cfg& b) {
     return a.go_rules == b.go_rules && a.go_komi == b.go_komi && a.go_chinese_rules == b.go_chinese_rules &&
            a.go_superko == b.go_superko;
@@ -191,11 +221,24 @@ static bool sameSearch(const az_search_cfg& a, const az_search_cfg& b) {   // al
 void ParallelMCTS::applyConfig() {
     const az_search_cfg c = deviceConfig();
     if (group_) {                          // the group's parameters are shared: other ones leave it
+        if (!sameSearchOptions(searchOptions(config_), group_->deviceOptions()))
+            throw std::invalid_argument("ParallelMCTS: a group member's search options (selection, depth cap, TD, widening) "
+                                        "differ from the group's");
         if (!sameSearch(c, group_->deviceConfig())) rebuild();
         return;
     }
+    // the search options in place, tree kept; refused ones (az_last_error says which) throw and change nothing
+    const az_search_opts o = searchOptions(config_);
+    if (s_) check(az_search_set_options(s_, &o), "az_search_set_options");
     if (s_ && az_search_set_params(s_, &c) == 0) return;
     rebuild();
+}
+
+// parallel_mcts.h:180: config_.selectionStrategy = strategy, the tree kept (az_search_set_params)
+void ParallelMCTS::setSelectionStrategy(MCTSNodeSelection s) {
+    const MCTSNodeSelection old = config_.selectionStrategy;
+    config_.selectionStrategy = s;
+    try { applyConfig(); } catch (...) { config_.selectionStrategy = old; throw; }
 }
 
 void ParallelMCTS::rebuild() {
@@ -216,6 +259,13 @@ void ParallelMCTS::rebuild() {
     const DeviceEvaluator ev = deviceEvaluator(nn_);
     const az_search_cfg c = deviceConfig();
     check(az_search_create(ev.engine, ev.net, &c, &s_), "az_search_create");
+    const az_search_opts o = searchOptions(config_);
+    if (az_search_set_options(s_, &o) != 0) {              // refused options: no handle is left behind
+        const std::string msg = az_last_error();
+        az_search_destroy(s_);
+        s_ = nullptr;
+        throw std::runtime_error("az_search_set_options: " + msg);
+    }
     if (c.eval_kind == AZ_EVAL_CALLBACK) check(az_search_set_evaluator(s_, &ParallelMCTS::hostEvaluate, this), "az_search_set_evaluator");
     const int g0 = 0;
     check(az_search_new_games(s_, &g0, 1), "az_search_new_games");
@@ -389,7 +439,11 @@ void ParallelMCTS::setTranspositionTable(TranspositionTable* tt) {
     }
     rebuild();
 }
-void ParallelMCTS::setConfig(const MCTSConfig& config) { config_ = config; applyConfig(); }
+void ParallelMCTS::setConfig(const MCTSConfig& config) {
+    const MCTSConfig old = config_;
+    config_ = config;
+    try { applyConfig(); } catch (...) { config_ = old; throw; }   // e.g. a group member with other options
+}
 // parallel_mcts.cpp:1263-1274: useBatchInference = enable; rng_ seeded 42, or from std::random_device
 void ParallelMCTS::setDeterministicMode(bool enable) {
     config_.deterministic = enable;

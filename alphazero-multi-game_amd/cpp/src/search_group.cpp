@@ -27,7 +27,14 @@ SearchGroup::SearchGroup(nn::NeuralNetwork* nn, const MCTSConfig& config, const 
         throw std::invalid_argument("SearchGroup: host-callback evaluators are not grouped (HipNeuralNetwork, "
                                     "RandomPolicyNetwork or no network)");
     cfg_ = makeSearchConfig(config, prototype, nn, tt, capacity);
+    opts_ = searchOptions(config);
     check(az_search_create(ev.engine, ev.net, &cfg_, &s_), "az_search_create");
+    if (az_search_set_options(s_, &opts_) != 0) {
+        const std::string msg = az_last_error();
+        az_search_destroy(s_);
+        s_ = nullptr;
+        throw std::runtime_error("az_search_set_options: " + msg);
+    }
 }
 
 SearchGroup::~SearchGroup() {

@@ -134,8 +134,16 @@ int SelfPlayManager::runGames(core::GameType type, int bs, bool variant, std::ve
     c.dirichlet_alpha = alpha_;
     c.dirichlet_eps = eps_;
     c.tt_log2 = 20;                                            // TranspositionTable tt(1048576), :159
+    // mctsConfig_'s search options; playSingleGame turns UCB into PUCT (:180-181)
+    mcts::MCTSConfig opts = mcts_;
+    if (opts.selectionStrategy == mcts::MCTSNodeSelection::UCB) opts.selectionStrategy = mcts::MCTSNodeSelection::PUCT;
+    const az_search_opts so = mcts::searchOptions(opts);
     az_search* s = nullptr;
     if (az_search_create(ev.engine, ev.net, &c, &s)) throw std::runtime_error(az_last_error());
+    if (az_search_set_options(s, &so)) {
+        az_search_destroy(s);
+        throw std::runtime_error(az_last_error());
+    }
     EvalCtx ectx{nn_, type, bs};
     if (ev.kind == AZ_EVAL_CALLBACK && az_search_set_evaluator(s, host_eval, &ectx)) {
         az_search_destroy(s);

@@ -70,6 +70,9 @@ struct az_search {
     TreeDev* d_tree = nullptr;
     Pinned<TreeDev> h_tree;
     int n_tree = 0, next_tree = 0;
+    az_search_opts opts{};          // the search options in force (az_search_set_options; creation: the defaults)
+    // the progressive-widening table t.wid_tab was built for (apply_search_opts)
+    bool wid_valid = false; float wid_base = 0.0f, wid_exponent = 0.0f; int wid_cap = 0;
     int64_t tree_evictions = 0;     // slot reuses (each a stream synchronisation): az_diag_tree_evictions
     // Dirichlet draws of the NEXT move, made on a host thread while the device searches this one
     // (prefetch_noise; Gomoku self-play): per game the child count they were drawn for (-1: none)

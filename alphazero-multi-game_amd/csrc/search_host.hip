@@ -6,6 +6,7 @@
 #include <sched.h>
 
 #include <algorithm>
+#include <climits>
 #include <cmath>
 #include <cstring>
 #include <functional>
@@ -67,7 +68,7 @@ int check_err(az_search* s) {
     HIPCHK(hipMemcpyAsync(&err, s->t.err, 4, hipMemcpyDeviceToHost, s->e->stream));
     if (s->net && s->c.eval_kind == AZ_EVAL_NET) HIPCHK(hipMemcpyAsync(&ovf, s->net->ovf, 4, hipMemcpyDeviceToHost, s->e->stream));
     HIPCHK(hipStreamSynchronize(s->e->stream));
-    if (err) return az_fail(AZ_ERR_CAPACITY, "device capacity exceeded (flags 0x%x: 1 node pool, 2 path, 4 prior ring)", err);
+    if (err) return az_fail(AZ_ERR_CAPACITY, "device capacity exceeded (flags 0x%x: 1 node pool, 2 path, 4 prior ring, 32 widening table)", err);
     if (int r = check_ovf(s->net, ovf)) return r;
     // per-slot nets: every other net's range guard (nets[0] is s->net, read above)
     for (int k = 1; k < s->n_nets; ++k) {
@@ -176,7 +177,8 @@ int search_step(az_search* s, int mode, bool pre = false, bool fuse_next = false
     const bool prof = s->prof && mode == MODE_SIM && s->prof_steps++ % prof_every() == 0 && s->pc.room(4);
     if (prof) s->pc.stamp(st);
     TREE_DEV(dts, s, s->t);
-    if (!pre) az_launch_select(dts, s->t.NA, s->t.G, mode, st);
+    const bool opt = tree_has_opts(s->t);
+    if (!pre) az_launch_select(dts, s->t.NA, s->t.G, mode, opt, st);
     if (prof) s->pc.stamp(st);
     if (s->c.eval_kind == AZ_EVAL_CALLBACK) {
         if (int r = host_evaluate(s)) return r;
@@ -216,11 +218,11 @@ int search_step(az_search* s, int mode, bool pre = false, bool fuse_next = false
         const bool fs = s->prof && mode == MODE_SIM && sidx % prof_every() == prof_every() / 2 && s->pcf.room(2);
         if (s->prof && mode == MODE_SIM) ++s->prof_fused_launches;
         if (fs) s->pcf.stamp(st);
-        az_launch_expand_select(dts, tt.eval_slot, tt.eval_identity, s->t.NA, G, st);
+        az_launch_expand_select(dts, tt.eval_slot, tt.eval_identity, s->t.NA, G, opt, st);
         if (fs) { s->pcf.stamp(st); ++s->prof_fused; }
     } else {
         TREE_DEV(dte, s, tt);
-        hipLaunchKernelGGL(k_expand_backup, dim3(G), dim3(64), 0, st, dte, mode);
+        az_launch_expand_backup(dte, G, mode, opt, st);
     }
     if (prof) { s->pc.stamp(st); s->prof_sampled += 1; }
     HIPCHK(hipGetLastError());
@@ -553,6 +555,63 @@ GoRules go_rules_of(const az_search_cfg& c) {
     return {c.go_komi, c.go_chinese_rules != 0, c.go_superko != 0};
 }
 bool same_rules(const GoRules& a, const GoRules& b) { return a.komi == b.komi && a.chinese == b.chinese && a.superko == b.superko; }
+
+// MCTSConfig's defaults (include/alphazero/mcts/parallel_mcts.h:47-58): what a new handle plays
+const az_search_opts kDefaultSearchOpts = {AZ_SEL_PUCT, 1000, 0, 0.8f, 0, 10, 2.0f, 0.5f};
+int check_widening(float base, float exponent) {
+    if (!std::isfinite(base) || base <= 0.0f) return az_fail(AZ_ERR_ARG, "widening_base must be finite and > 0");
+    if (!(exponent > 0.0f && exponent <= 1.0f)) return az_fail(AZ_ERR_ARG, "widening_exponent must lie in (0, 1]");
+    return 0;
+}
+int check_search_opts(const az_search_opts& o) {
+    if (o.selection < AZ_SEL_UCB || o.selection > AZ_SEL_RAVE)
+        return az_fail(AZ_ERR_ARG, "selection %d: 0 UCB, 1 PUCT, 2 PROGRESSIVE_BIAS, 3 RAVE", o.selection);
+    if (!std::isfinite(o.td_lambda)) return az_fail(AZ_ERR_ARG, "td_lambda must be finite");
+    return check_widening(o.widening_base, o.widening_exponent);
+}
+// largest widening table (entries); az_diag_set_widening_cap lowers it for the capacity test
+int g_widening_cap = 1 << 22;
+
+// getProgressiveWideningCount(N, n_actions) (parallel_mcts.cpp:1299-1313) for N = 0, 1, ... up to the first
+// N whose count reaches n_actions, at most cap entries: the reference's expression -- a float base times
+// std::pow(int, float), i.e. the double pow of the host libm -- with the x86-64 conversion of a NaN or
+// out-of-range double (INT_MIN) spelled out
+void widening_table(float base, float exponent, int n_actions, int cap, std::vector<int>& tab) {
+    tab.clear();
+    for (int N = 0; (int)tab.size() < cap; ++N) {
+        const double x = base * std::pow(N, exponent);
+        const int raw = (x > -2147483649.0 && x < 2147483648.0) ? static_cast<int>(x) : INT_MIN;
+        const int count = std::max(1, std::min(raw, n_actions));
+        tab.push_back(count);
+        if (count >= n_actions) break;
+    }
+}
+
+// The options into the TreeDev with their widening table (a new device buffer; the old one is
+// released after the stream has drained: no queued kernel reads it then)
+int apply_search_opts(az_search* s, const az_search_opts& o) {
+    TreeDev& t = s->t;
+    const bool retab = o.use_widening && (!t.wid_tab || !s->wid_valid || o.widening_base != s->wid_base ||
+                                          o.widening_exponent != s->wid_exponent || g_widening_cap != s->wid_cap);
+    if (retab) {
+        std::vector<int> tab;
+        widening_table(o.widening_base, o.widening_exponent, t.NA, g_widening_cap, tab);
+        int* d = nullptr;
+        if (int r = s->pool.alloc(&d, tab.size())) return r;
+        if (hipMemcpy(d, tab.data(), tab.size() * 4, hipMemcpyHostToDevice) != hipSuccess ||
+            hipStreamSynchronize(s->e->stream) != hipSuccess) {
+            s->pool.release(d);
+            return az_fail(AZ_ERR_HIP, "widening table upload failed");
+        }
+        s->pool.release(t.wid_tab);
+        t.wid_tab = d; t.wid_len = (int)tab.size(); t.wid_complete = tab.back() >= t.NA;
+        s->wid_valid = true; s->wid_base = o.widening_base; s->wid_exponent = o.widening_exponent; s->wid_cap = g_widening_cap;
+    }
+    t.sel = o.selection; t.max_depth = o.max_search_depth; t.use_td = o.use_td; t.td_lambda = o.td_lambda;
+    t.use_wid = o.use_widening; t.wid_min = o.widening_min_visits;
+    s->opts = o;
+    return 0;
+}
 }  // namespace
 
 // az_search_create with the batch capacity asked of `net` given apart from the number of games: the
@@ -668,6 +727,7 @@ int search_create(az_engine* e, az_net* net, const az_search_cfg* c, int net_bat
         HIPCHK(hipMemcpy(fo, order.data(), A * 4, hipMemcpyHostToDevice));
     }
     HIPCHK(hipMemset(t.err, 0, 4));
+    if (int r2 = apply_search_opts(s, kDefaultSearchOpts)) return r2;
     if (s->pool.alloc(&s->d_tree, AZ_TREE_SLOTS) || !s->h_tree.get(AZ_TREE_SLOTS)) return az_fail(AZ_ERR_OOM, "TreeDev slots");
     HIPCHK(hipDeviceSynchronize());   // the null-stream copies / memsets above, before the engine stream runs
     // every slot an idle game with a valid root until k_new_games starts it
@@ -1007,6 +1067,41 @@ int az_search_set_params(az_search* s, const az_search_cfg* c) {
     s->c.noise_seed = c->noise_seed; s->c.noise_seed_stride = c->noise_seed_stride;
     s->t.cpuct = c->c_puct; s->t.fpu = c->fpu_reduction; s->t.vl = c->virtual_loss;
     return 0;
+}
+
+int az_search_set_options(az_search* s, const az_search_opts* opts) {
+    if (!s) return az_fail(AZ_ERR_ARG, "null search");
+    az_search_opts o = opts ? *opts : kDefaultSearchOpts;
+    o.use_td = o.use_td != 0; o.use_widening = o.use_widening != 0;
+    if (int r = check_search_opts(o)) return r;
+    std::lock_guard<std::mutex> lk(s->mu);
+    HIPCHK(hipSetDevice(s->e->device));
+    return apply_search_opts(s, o);
+}
+
+int az_search_options(az_search* s, az_search_opts* out) {
+    if (!s || !out) return az_fail(AZ_ERR_ARG, "null argument");
+    std::lock_guard<std::mutex> lk(s->mu);
+    *out = s->opts;
+    return 0;
+}
+
+int az_search_widening_table(float base, float exponent, int n_actions, int* out, int cap, int* len) {
+    if (!len || cap < 0 || (cap > 0 && !out)) return az_fail(AZ_ERR_ARG, "null argument");
+    if (n_actions < 1 || n_actions > AZ_MAXNA) return az_fail(AZ_ERR_ARG, "n_actions %d outside 1..%d", n_actions, AZ_MAXNA);
+    if (int r = check_widening(base, exponent)) return r;
+    std::vector<int> tab;
+    widening_table(base, exponent, n_actions, g_widening_cap, tab);
+    *len = (int)tab.size();
+    std::copy(tab.begin(), tab.begin() + std::min<size_t>(tab.size(), (size_t)cap), out);
+    return 0;
+}
+
+// Diagnostic (tests): the largest widening table from now on, 1 .. 2^22 entries; returns the limit it replaced.
+int az_diag_set_widening_cap(int entries) {
+    const int old = g_widening_cap;
+    g_widening_cap = std::max(1, std::min(entries, 1 << 22));
+    return old;
 }
 
 int az_search_go_rules(az_search* s, float* komi, int* chinese_rules, int* superko) {

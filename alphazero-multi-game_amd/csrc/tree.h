@@ -24,7 +24,9 @@ enum { MODE_SIM = 0, MODE_ROOT_NOISE = 1, MODE_ROOT_SEARCH = 2 };
 enum { FL_EXPANDED = 1, FL_TERMINAL = 2 };   // result (GameResult) in bits 2..3
 enum { CNT_EVALS = 0, CNT_LOOKUPS = 1, CNT_HITS = 2, CNT_SIMS = 3, CNT_NODES = 4, CNT_EVALS_TOTAL = 5,
        CNT_BYTES_SEL = 6, CNT_BYTES_EXP = 7 };   // [5..7] survive new games; 6/7: algorithmic HBM bytes of K1 / K3
-enum { ERR_NODES = 1, ERR_PATH = 2, ERR_RING = 4, ERR_BATCH = 8, ERR_HIST = 16 };
+enum { ERR_NODES = 1, ERR_PATH = 2, ERR_RING = 4, ERR_BATCH = 8, ERR_HIST = 16, ERR_WIDEN = 32 };
+// MCTSNodeSelection (include/alphazero/mcts/parallel_mcts.h:26-31); RAVE plays PUCT (selectChildRave)
+enum { SEL_UCB = 0, SEL_PUCT = 1, SEL_PROGRESSIVE_BIAS = 2, SEL_RAVE = 3 };
 enum { GAME_GOMOKU = 0, GAME_GO = 1 };
 
 struct Nodes {          // one arena: [G][ncap]
@@ -79,15 +81,29 @@ struct TreeDev {
     const float* net_logits;     // [B][A] (NET) raw policy logits, by eval slot
     const float* net_value;      // [B]
     int log_game, log_cap; float* log_pol; float* log_val; float* log_planes; int* log_n;
+    // Search options (az_search_opts, az_search_set_options; MCTSConfig): read only by the kernels' OPT instantiations,
+    // which the host launches when tree_has_opts(); the default instantiations never look at them.
+    // wid_tab[N], N in [0, wid_len): getProgressiveWideningCount(N, NA) (az_search_widening_table);
+    // wid_complete: its last entry reached NA, so every count past it is "all children"
+    int sel, max_depth, use_td; float td_lambda;
+    int use_wid, wid_min, wid_len, wid_complete;
+    const int* wid_tab;
     int stamp_game;              // diagnostic: this game's k_select / k_expand_backup write phase stamps (-1 off)
     int pad2 = 0;
 };
+// the options that need the OPT kernels (RAVE and a cap the path capacity reaches first are the default search)
+inline bool tree_has_opts(const TreeDev& t) {
+    return t.sel == SEL_UCB || t.sel == SEL_PROGRESSIVE_BIAS || t.max_depth < AZ_DMAX || t.use_td || t.use_wid;
+}
 // no implicit padding: every byte of a TreeDev is a member (tree_dev() finds a variant with memcmp)
 static_assert(offsetof(TreeDev, zko) == offsetof(TreeDev, pad0) + sizeof(int), "TreeDev hole after pad0");
 static_assert(offsetof(TreeDev, gresult) == offsetof(TreeDev, pad3) + sizeof(int), "TreeDev hole after pad3");
 static_assert(offsetof(TreeDev, komi) == offsetof(TreeDev, zconst) + sizeof(uint64_t), "TreeDev hole before komi");
 static_assert(offsetof(TreeDev, leafrec) == offsetof(TreeDev, pad1) + sizeof(int), "TreeDev hole after pad1");
 static_assert(sizeof(TreeDev) == offsetof(TreeDev, pad2) + sizeof(int), "TreeDev tail padding");
+static_assert(offsetof(TreeDev, wid_tab) == offsetof(TreeDev, sel) + 8 * sizeof(int), "TreeDev hole before wid_tab");
+static_assert(offsetof(TreeDev, sel) == offsetof(TreeDev, log_n) + sizeof(int*), "TreeDev hole before sel");
+static_assert(offsetof(TreeDev, stamp_game) == offsetof(TreeDev, wid_tab) + sizeof(int*), "TreeDev hole after wid_tab");
 static_assert(offsetof(TreeDev, tt_mask) == 10 * sizeof(int), "TreeDev hole before tt_mask");
 
 // Training-example extraction (Dataset::extractExamples + augmentExample).

@@ -6,11 +6,14 @@
 
 #include "tree.h"
 
-void az_launch_select(const TreeDev* t, int NA, int G, int mode, hipStream_t st);
-void az_launch_expand_select(const TreeDev* ts, const int* eval_slot, int eval_identity, int NA, int G, hipStream_t st);
+// opt: tree_has_opts() of the TreeDev behind the device pointer -- the kernels' instantiation with the
+// search options (selection strategy, depth cap, TD backup, progressive widening); false: the plain search
+void az_launch_select(const TreeDev* t, int NA, int G, int mode, bool opt, hipStream_t st);
+void az_launch_expand_select(const TreeDev* ts, const int* eval_slot, int eval_identity, int NA, int G, bool opt,
+                             hipStream_t st);
+void az_launch_expand_backup(const TreeDev* t, int G, int mode, bool opt, hipStream_t st);
 __global__ void k_scan(const TreeDev* __restrict__ tp);
 __global__ void k_scan_nets(const TreeDev* __restrict__ tp, const uint8_t* __restrict__ slot_net, int n_nets);
-__global__ void k_expand_backup(const TreeDev* __restrict__ tp, int mode);
 __global__ void k_select_action(const TreeDev* __restrict__ tp, int training, float temperature, const float* temps, int* actions, float* values, float* probs,
                                 int* child_actions, int* nchild);
 __global__ void k_apply(TreeDev t, const int* actions, int* terminal, int* result, int* rexp);

@@ -212,6 +212,27 @@ __device__ __forceinline__ float puct_score(int visits, float W, int VL, float P
     return q + u + div;
 }
 
+// getProgressiveBiasScore (mcts_node.cpp:121-166): getAdjustedValue (:479-491) with getPuctScore's
+// depth-1 negation, cPuct * prior * max(0.1, 1 / sqrt(1 + N)) and, for Go only, 0.02 * parentVisits /
+// (1 + N); no FPU and no diversity term.  std::max(0.1f, x) keeps 0.1f when x is NaN (N < -1).
+__device__ __forceinline__ float pbias_score(int visits, float W, int VL, float P, int parentDepth, int pN, float cpuct,
+                                             bool go) {
+    if (visits == 0) return FLT_MAX;
+    const int act = visits - VL;
+    float q = act <= 0 ? 0.0f : W / (float)act;
+    if (parentDepth == 1) q = -q;
+    const float r = 1.0f / sqrtf(1.0f + (float)visits);
+    const float w = 0.1f < r ? r : 0.1f;
+    const float e = cpuct * P * w;
+    float gb = 0.0f;
+    if (go) gb = 0.02f * (float)pN / (1.0f + (float)visits);
+    return q + e + gb;
+}
+// getUcbScore (mcts_node.cpp:38-59): FLT_MAX unvisited, else the constant 0.5f + 1.5f * 0.5f *
+// sqrt(1.0f) / (1.0f + 1.0f).  Every score exceeds -FLT_MAX, so selectChildUcb's random pick
+// (parallel_mcts.cpp:589-599) is never reached and rng_ is not drawn.
+__device__ __forceinline__ float ucb_score(int visits) { return visits == 0 ? FLT_MAX : 0.875f; }
+
 // HashEvaluator key (oracle/ref_harness.cpp hash_eval)
 __device__ uint64_t hash_eval_key(uint64_t zhash, const int* hist6) {
     uint64_t key = splitmix64(zhash ^ 0x5A17C0DEULL);
@@ -680,7 +701,9 @@ struct ExpLds {
     float s_scalar[2];
 };
 
-template <int IT>
+// OPT: the search options of az_search_cfg (TreeDev sel / max_depth / use_wid ...) are in force; the
+// default instantiation (OPT = false) is the plain PUCT search and reads none of them.
+template <int IT, bool OPT>
 __device__ __forceinline__ void select_game(const TreeDev& t, int mode, const RootHint* hint, SelLds& SL, GoLds& gl) {
     const int g = blockIdx.x;
     const int lane = threadIdx.x;
@@ -718,6 +741,7 @@ __device__ __forceinline__ void select_game(const TreeDev& t, int mode, const Ro
     int status = ST_NONE;
     float value = 0.0f;
     long long scanned = 0;       // child records read by the PUCT scans (25 B each)
+    int widened = 0;             // children progressive widening decremented and wrote back (12 B each)
     const bool hv = hint && hint->valid;
     int4 rhdr0 = int4{0, 0, 0, 0};
     uint8_t nflag = hv ? (uint8_t)hint->flag : nd.flag[root];   // flag of the current node (the leaf's after the descent)
@@ -740,10 +764,19 @@ __device__ __forceinline__ void select_game(const TreeDev& t, int mode, const Ro
         tstamp(t, g, 0, 1);
         int pN = rN, pVL = rVL;
         float pW = rW;
+        const int maxd = OPT ? t.max_depth : 1000;      // maxSearchDepth (parallel_mcts.cpp:469)
         while (true) {
-            if (!(nflag & FL_EXPANDED) || (nflag & FL_TERMINAL) || depth >= 1000 || nc <= 0) break;
+            if (!(nflag & FL_EXPANDED) || (nflag & FL_TERMINAL) || depth >= maxd || nc <= 0) break;
             scanned += nc;
             const float sq = sqrtf((float)pN);
+            // getProgressiveWideningCount(pN, nc) (parallel_mcts.cpp:1299-1313) from the host's table,
+            // loaded with the level's child records: 1 at pN <= 0, every child past a complete table
+            int wcount = nc;
+            if (OPT && t.use_wid) {
+                if (pN <= 0) wcount = 1;
+                else if (pN < t.wid_len) wcount = min(t.wid_tab[pN], nc);
+                else if (!t.wid_complete && lane == 0) atomicOr(t.err, ERR_WIDEN);
+            }
             int cN[IT], cVL[IT], cF[IT], cC[IT], cA[IT], cFl[IT];
             float cW[IT], cP[IT];
 #pragma unroll
@@ -752,13 +785,32 @@ __device__ __forceinline__ void select_game(const TreeDev& t, int mode, const Ro
                 cN[k] = nd.N[c]; cW[k] = nd.W[c]; cVL[k] = nd.VL[c]; cP[k] = nd.P[c];
                 cF[k] = nd.first[c]; cC[k] = nd.cnt[c]; cA[k] = nd.act[c]; cFl[k] = nd.flag[c];
             }
+            int lim = nc;                                  // children the argmax looks at
+            bool dec[IT];
+            if (OPT && t.use_wid) {
+                // selectLeafWithPath (:471-485): every child i >= count that has visitCount < 1 gets
+                // addVirtualLoss(-virtualLoss) -- N -= vl, VL -= vl, W - (float)(-vl) -- on every pass,
+                // before the children are scored; the scan stops at count only from minVisitsForWidening
+                // parent visits on (:545-552), so below that a child just decremented can be picked
+                const bool cut = nc > 1 && wcount < nc;
+#pragma unroll
+                for (int k = 0; k < IT; ++k) {
+                    const int i = lane + 64 * k;
+                    dec[k] = cut && i < nc && i >= wcount && cN[k] < 1;
+                    if (dec[k]) { cN[k] -= t.vl; cVL[k] -= t.vl; cW[k] = cW[k] - (float)(-t.vl); }
+                }
+                if (pN >= t.wid_min) lim = wcount;
+            }
             float best = -FLT_MAX;
             int bi = INT_MAX, bk = 0;
 #pragma unroll
             for (int k = 0; k < IT; ++k) {
                 const int i = lane + 64 * k;
-                if (i < nc) {
-                    float s = puct_score(cN[k], cW[k], cVL[k], cP[k], depth, pN, pVL, pW, t.cpuct, t.fpu, sq);
+                if (i < lim) {
+                    float s;
+                    if (OPT && t.sel == SEL_UCB) s = ucb_score(cN[k]);
+                    else if (OPT && t.sel == SEL_PROGRESSIVE_BIAS) s = pbias_score(cN[k], cW[k], cVL[k], cP[k], depth, pN, t.cpuct, go);
+                    else s = puct_score(cN[k], cW[k], cVL[k], cP[k], depth, pN, pVL, pW, t.cpuct, t.fpu, sq);
                     if (s > best) { best = s; bi = i; bk = k; }
                 }
             }
@@ -768,6 +820,17 @@ __device__ __forceinline__ void select_game(const TreeDev& t, int mode, const Ro
             for (int k = 1; k < IT; ++k)
                 if (bk == k) { bN = cN[k]; bVL = cVL[k]; bF = cF[k]; bC = cC[k]; bA = cA[k]; bFl = cFl[k]; bW = cW[k]; }
             wave_argmax(best, bi);
+            if (OPT && t.use_wid) {
+                // the decremented children back to the tree, lane-parallel; the selected one is a path
+                // node: its statistics are written with the virtual loss below
+#pragma unroll
+                for (int k = 0; k < IT; ++k) {
+                    const int i = lane + 64 * k;
+                    const bool w = dec[k] && i != bi;
+                    if (w) { const int c = fc + i; nd.N[c] = cN[k]; nd.VL[c] = cVL[k]; nd.W[c] = cW[k]; }
+                    widened += __popcll(__ballot(w));
+                }
+            }
             if (bi == INT_MAX) break;
             if (depth + 1 >= AZ_DMAX) { if (lane == 0) atomicOr(t.err, ERR_PATH); break; }
             const int src = bi & 63;
@@ -941,27 +1004,36 @@ __device__ __forceinline__ void select_game(const TreeDev& t, int mode, const Ro
         long long b = scanned * 25 + 21 + (long long)(depth + 1) * (24 + 8 + 8) + t.A + 12;
         if (status == ST_TTHIT) b += 20;
         if (status == ST_EVAL) b += (go ? 2LL : 1LL) * t.A + 32;
+        if (OPT) b += 12LL * widened;                   // progressive widening's decrement writes
         cnt[CNT_BYTES_SEL] = c_bytes + b;
     }
     tstamp(t, g, 0, 7);
 }
 
-template <int IT>
+template <int IT, bool OPT>
 __global__ __launch_bounds__(64) void k_select(const TreeDev* __restrict__ tp, int mode) {
     const TreeDev& t = *tp;                               // device-resident (tree_dev, search_host.hip): an 8-byte kernarg
     __shared__ SelLds SL;
     __shared__ GoLds gl;
-    select_game<IT>(t, mode, nullptr, SL, gl);
+    select_game<IT, OPT>(t, mode, nullptr, SL, gl);
 }
 
 extern "C" int az_diag_tree_stamps(unsigned long long* out, int n) {
     return hipMemcpyFromSymbol(out, HIP_SYMBOL(g_tree_stamps), sizeof(unsigned long long) * (n < 128 ? n : 128)) == hipSuccess ? 0 : -1;
 }
 
-void az_launch_select(const TreeDev* t, int NA, int G, int mode, hipStream_t st) {
-    if (NA <= 128) hipLaunchKernelGGL(k_select<2>, dim3(G), dim3(64), 0, st, t, mode);
-    else if (NA <= 256) hipLaunchKernelGGL(k_select<4>, dim3(G), dim3(64), 0, st, t, mode);
-    else hipLaunchKernelGGL(k_select<(AZ_MAXNA + 63) / 64>, dim3(G), dim3(64), 0, st, t, mode);
+namespace {
+template <bool OPT>
+void launch_select(const TreeDev* t, int NA, int G, int mode, hipStream_t st) {
+    if (NA <= 128) hipLaunchKernelGGL((k_select<2, OPT>), dim3(G), dim3(64), 0, st, t, mode);
+    else if (NA <= 256) hipLaunchKernelGGL((k_select<4, OPT>), dim3(G), dim3(64), 0, st, t, mode);
+    else hipLaunchKernelGGL((k_select<(AZ_MAXNA + 63) / 64, OPT>), dim3(G), dim3(64), 0, st, t, mode);
+}
+}  // namespace
+// opt: tree_has_opts() of the TreeDev behind t (the launchers take device pointers)
+void az_launch_select(const TreeDev* t, int NA, int G, int mode, bool opt, hipStream_t st) {
+    if (opt) launch_select<true>(t, NA, G, mode, st);
+    else launch_select<false>(t, NA, G, mode, st);
 }
 
 // Host evaluator: the moves from the root to every leaf of the evaluation batch (slot order).
@@ -1059,6 +1131,7 @@ __global__ __launch_bounds__(1024) void k_scan_nets(const TreeDev* __restrict__ 
 // then the leaf's network outputs and the path nodes' statistics -- the second and last one.
 // The Gomoku leaf board is the root board plus the path moves (no Zobrist work: k_select stored
 // the leaf hash); a Go leaf's position comes back from the state k_select stored (go_load_leaf).
+template <bool OPT>
 __device__ __forceinline__ void expand_game(const TreeDev& t, int mode, ExpLds& EL, GoLds& gl, RootHint* hint = nullptr) {
     const int g = blockIdx.x;
     const int lane = threadIdx.x;
@@ -1354,8 +1427,28 @@ __device__ __forceinline__ void expand_game(const TreeDev& t, int mode, ExpLds& 
         // nodes are distinct and each gets its own unchanged sequence of fp32 operations, so the
         // update runs one lane per node (bit-identical to the sequential walk) on the statistics
         // loaded in round trip 2 (nothing in this kernel writes a path node's N / VL / W before).
+        float v0 = ((depth - lane) & 1) ? -value : value;
+        float v1 = ((depth - lane - 64) & 1) ? -value : value;
+        if (OPT && t.use_td) {
+            // TD(lambda) (:825-831): after node i's update the value is negated and, unless node i is
+            // the root, becomes (1 - lambda) * (-parent.getValue()) + lambda * value -- two products and
+            // a sum -- with the parent (node i - 1) not yet updated and its virtual loss still on: the
+            // pstat statistics.  The parents' terms are lane-parallel; the recurrence over the path is
+            // sequential (wave-uniform, the terms read lane by lane).
+            const float om = 1.0f - t.td_lambda;
+            const float a0 = om * -(bN0 == 0 ? 0.0f : bW0 / (float)bN0);
+            const float a1 = om * -(bN1 == 0 ? 0.0f : bW1 / (float)bN1);
+            float cv = value;
+            if (lane == (depth & 63)) { if (depth < 64) v0 = cv; else v1 = cv; }
+            for (int i = depth; i >= 1; --i) {
+                const int j = i - 1;
+                const float a = lane_bcast(j < 64 ? a0 : a1, j & 63);
+                cv = a + t.td_lambda * -cv;
+                if (lane == (j & 63)) { if (j < 64) v0 = cv; else v1 = cv; }
+            }
+        }
         if (lane <= depth) {
-            const float v = ((depth - lane) & 1) ? -value : value;
+            const float v = v0;
             int N = bN0 - t.vl, VL = bVL0 - t.vl;
             float W = bW0 + (float)t.vl;                   // removeVirtualLoss
             N += 1;
@@ -1367,7 +1460,7 @@ __device__ __forceinline__ void expand_game(const TreeDev& t, int mode, ExpLds& 
             }
         }
         if (lane + 64 <= depth) {
-            const float v = ((depth - lane - 64) & 1) ? -value : value;
+            const float v = v1;
             int N = bN1 - t.vl, VL = bVL1 - t.vl;
             float W = bW1 + (float)t.vl;
             N += 1;
@@ -1383,11 +1476,16 @@ __device__ __forceinline__ void expand_game(const TreeDev& t, int mode, ExpLds& 
     tstamp(t, g, 1, 7);
 }
 
+template <bool OPT>
 __global__ __launch_bounds__(64) void k_expand_backup(const TreeDev* __restrict__ tp, int mode) {
     const TreeDev& t = *tp;
     __shared__ ExpLds EL;
     __shared__ GoLds gl;
-    expand_game(t, mode, EL, gl);
+    expand_game<OPT>(t, mode, EL, gl);
+}
+void az_launch_expand_backup(const TreeDev* t, int G, int mode, bool opt, hipStream_t st) {
+    if (opt) hipLaunchKernelGGL(k_expand_backup<true>, dim3(G), dim3(64), 0, st, t, mode);
+    else hipLaunchKernelGGL(k_expand_backup<false>, dim3(G), dim3(64), 0, st, t, mode);
 }
 
 // K3 of simulation step i and K1 of step i+1 in one launch: a game's expansion / backup and its
@@ -1396,7 +1494,7 @@ __global__ __launch_bounds__(64) void k_expand_backup(const TreeDev* __restrict_
 // after the block barrier's release / acquire).  te: step i's batch maps, ts: the search's.
 // One TreeDev argument (the kernel's scalar registers are the tight resource): the expansion's
 // batch map differs from the search's only in eval_slot / eval_identity.
-template <int IT>
+template <int IT, bool OPT>
 __global__ __launch_bounds__(64) void k_expand_select(const TreeDev* __restrict__ tsp, const int* eval_slot, int eval_identity) {
     const TreeDev& ts = *tsp;
     __shared__ RootHint hint;
@@ -1405,15 +1503,23 @@ __global__ __launch_bounds__(64) void k_expand_select(const TreeDev* __restrict_
     TreeDev te = ts;
     te.eval_slot = const_cast<int*>(eval_slot);
     te.eval_identity = eval_identity;
-    expand_game(te, MODE_SIM, U.e, gl, &hint);
+    expand_game<OPT>(te, MODE_SIM, U.e, gl, &hint);
     __syncthreads();                                      // the expansion's LDS is the selection's from here
-    select_game<IT>(ts, MODE_SIM, &hint, U.s, gl);
+    select_game<IT, OPT>(ts, MODE_SIM, &hint, U.s, gl);
 }
 
-void az_launch_expand_select(const TreeDev* ts, const int* eval_slot, int eval_identity, int NA, int G, hipStream_t st) {
-    if (NA <= 128) hipLaunchKernelGGL(k_expand_select<2>, dim3(G), dim3(64), 0, st, ts, eval_slot, eval_identity);
-    else if (NA <= 256) hipLaunchKernelGGL(k_expand_select<4>, dim3(G), dim3(64), 0, st, ts, eval_slot, eval_identity);
-    else hipLaunchKernelGGL(k_expand_select<(AZ_MAXNA + 63) / 64>, dim3(G), dim3(64), 0, st, ts, eval_slot, eval_identity);
+namespace {
+template <bool OPT>
+void launch_expand_select(const TreeDev* ts, const int* eval_slot, int eval_identity, int NA, int G, hipStream_t st) {
+    if (NA <= 128) hipLaunchKernelGGL((k_expand_select<2, OPT>), dim3(G), dim3(64), 0, st, ts, eval_slot, eval_identity);
+    else if (NA <= 256) hipLaunchKernelGGL((k_expand_select<4, OPT>), dim3(G), dim3(64), 0, st, ts, eval_slot, eval_identity);
+    else hipLaunchKernelGGL((k_expand_select<(AZ_MAXNA + 63) / 64, OPT>), dim3(G), dim3(64), 0, st, ts, eval_slot, eval_identity);
+}
+}  // namespace
+void az_launch_expand_select(const TreeDev* ts, const int* eval_slot, int eval_identity, int NA, int G, bool opt,
+                             hipStream_t st) {
+    if (opt) launch_expand_select<true>(ts, eval_slot, eval_identity, NA, G, st);
+    else launch_expand_select<false>(ts, eval_slot, eval_identity, NA, G, st);
 }
 
 // K4: visit distribution, action choice and root value per game.

@@ -198,11 +198,35 @@ typedef struct az_search_cfg {
                              opponent's captures as the reference does (go_rules.cpp:336-353) */
     int go_superko;       /* != 0: positional superko over the game's positions; 0: the ko point only */
 } az_search_cfg;
+/* Search options (MCTSConfig, include/alphazero/mcts/parallel_mcts.h:47-58), a struct of their own:
+ * az_search_cfg keeps its layout.  A new handle plays the defaults -- PUCT, depth cap 1000, no TD
+ * (lambda 0.8), no widening (10 visits, base 2.0, exponent 0.5); az_search_set_options puts others in
+ * force, at once after creation or on a live handle, trees kept (setSelectionStrategy / setConfig,
+ * parallel_mcts.h:172-182).  Refused with AZ_ERR_ARG, the handle as it was: selection outside 0..3, a
+ * non-finite td_lambda, widening_base not finite or <= 0, widening_exponent outside (0, 1] (where the
+ * reference's count is neither monotone nor defined: a stated deviation). */
+typedef struct az_search_opts {
+    int selection;        /* MCTSNodeSelection: 0 UCB, 1 PUCT, 2 PROGRESSIVE_BIAS, 3 RAVE (plays PUCT, as
+                             selectChildRave does, parallel_mcts.cpp:631-634) */
+    int max_search_depth; /* maxSearchDepth: the descent stops at this depth (parallel_mcts.cpp:469); <= 0
+                             makes the root the leaf; a path longer than the device's capacity is
+                             AZ_ERR_CAPACITY as before */
+    int use_td;           /* useTemporalDifference: the TD(lambda) backup of parallel_mcts.cpp:825-831 */
+    float td_lambda;      /* tdLambda (1: bitwise the plain backup) */
+    int use_widening;     /* useProgressiveWidening (parallel_mcts.cpp:471-485, 545-552, 1299-1313) */
+    int widening_min_visits;   /* minVisitsForWidening */
+    float widening_base;       /* progressiveWideningBase */
+    float widening_exponent;   /* progressiveWideningExponent */
+} az_search_opts;
 
 #define AZ_GAME_GOMOKU 0
 #define AZ_GAME_GO 1
 #define AZ_ACTION_NONE (-2)   /* Go: no move (finished game); -1 is the pass */
 #define AZ_GO_RULES_SET 1
+#define AZ_SEL_UCB 0
+#define AZ_SEL_PUCT 1
+#define AZ_SEL_PROGRESSIVE_BIAS 2
+#define AZ_SEL_RAVE 3
 
 int az_search_create(az_engine* e, az_net* net, const az_search_cfg* cfg, az_search** out);
 /* AZ_EVAL_CALLBACK: every simulation step hands the n leaves that need an evaluation to the host,
@@ -270,9 +294,27 @@ int az_search_root_node(az_search* s, int game, int* N, int* VL, float* W);
 /* Update the search parameters of a live handle without touching its trees (the reference's
  * setters / setConfig keep the tree, parallel_mcts.h:172-182, parallel_mcts.cpp:1225-1261):
  * num_simulations (up to the node pool sized at creation, else AZ_ERR_CAPACITY), c_puct,
- * fpu_reduction, virtual_loss, the Dirichlet fields and the noise seeds of later new games.
+ * fpu_reduction, virtual_loss, the Dirichlet fields and the noise seeds of later new games.  The search
+ * options (az_search_set_options) stay as they are.
  * Shape, evaluator and table changes need a new handle (AZ_ERR_ARG). */
 int az_search_set_params(az_search* s, const az_search_cfg* cfg);
+/* The search options of a handle (every game slot plays them), trees kept; a new widening table is
+ * uploaded when the widening parameters change.  opts null: back to the defaults. */
+int az_search_set_options(az_search* s, const az_search_opts* opts);
+/* The search options the handle plays (the defaults on a handle that was never given any). */
+int az_search_options(az_search* s, az_search_opts* out);
+/* Host only (no device needed): the progressive-widening counts the device reads,
+ * table[N] = max(1, min((int)(base * std::pow(N, exponent)), n_actions)) in the reference's own
+ * expression (getProgressiveWideningCount, parallel_mcts.cpp:1299-1313: a float base times a double
+ * pow, the host libm) for N = 0, 1, ... up to the first N whose count reaches n_actions; past that N,
+ * and at N <= 0, the count needs no table (every child; 1).  *len = the table's length, at most
+ * 2^22 entries (a table cut there is incomplete: its last entry is below n_actions, and a visit count
+ * past it is AZ_ERR_CAPACITY on the device); min(*len, cap) entries are written to out (out may be
+ * null with cap 0).  AZ_ERR_ARG for parameters az_search_set_options refuses. */
+int az_search_widening_table(float base, float exponent, int n_actions, int* out, int cap, int* len);
+/* Diagnostic (tests of the capacity error): the largest widening table built from now on, 1 .. 2^22
+ * entries; returns the limit it replaced. */
+int az_diag_set_widening_cap(int entries);
 /* The Go rules the handle plays (the defaults spelled out when it was created with go_rules 0; a
  * Gomoku handle reports the defaults): what a host object hands to the handle it rebuilds. */
 int az_search_go_rules(az_search* s, float* komi, int* chinese_rules, int* superko);
