@@ -18,7 +18,7 @@ from dataclasses import dataclass, field
 
 import numpy as np
 
-from ._lib import (AZ_GO_RULES_SET, AZ_SEL_PROGRESSIVE_BIAS, AZ_SEL_PUCT, AZ_SEL_RAVE, AZ_SEL_UCB, SearchOpts, AZ_EVAL_CALLBACK, AZ_EVAL_HASH, AZ_EVAL_NET, AZ_EVAL_RANDOM, AZ_EVAL_UNIFORM, EVAL_FN, AZ_PREC_BF16, AZ_PREC_BF16X3, AZ_PREC_F16X3, AZ_PREC_F32, AZ_PREC_FP16, AzError,
+from ._lib import (AZ_GO_RULES_SET, GomokuRules, AZ_SEL_PROGRESSIVE_BIAS, AZ_SEL_PUCT, AZ_SEL_RAVE, AZ_SEL_UCB, SearchOpts, AZ_EVAL_CALLBACK, AZ_EVAL_HASH, AZ_EVAL_NET, AZ_EVAL_RANDOM, AZ_EVAL_UNIFORM, EVAL_FN, AZ_PREC_BF16, AZ_PREC_BF16X3, AZ_PREC_F16X3, AZ_PREC_F32, AZ_PREC_FP16, AzError,
                    ARENA_SINK, ArenaCfg, ArenaSummary, GAME_SINK, PROGRESS_FN, MoveRec as _lib_MoveRec, NetDesc, SearchCfg, SelfPlayCfg, check, lib)
 
 __all__ = ["Engine", "HipNeuralNetwork", "ParallelMCTS", "SelfPlayManager", "Arena", "ArenaGameRecord", "EloRating", "GameRecord", "MoveData", "AzError",
@@ -245,10 +245,12 @@ class ParallelMCTS:
                  virtual_loss=3, evaluator=AZ_EVAL_HASH, net=None, eval_seed=7, zobrist_seed=12345, noise_seed=42,
                  noise_seed_stride=0, use_dirichlet_each_search=False, dirichlet_alpha=0.03, dirichlet_eps=0.25,
                  tt_log2=20, node_capacity=0, prior_ring=0, game=0, callback=None, go_komi=7.5, go_chinese_rules=True,
-                 go_superko=True, **search_opts):
+                 go_superko=True, gomoku_renju=False, gomoku_omok=False, **search_opts):
         """game: AZ_GAME_GOMOKU (0) or AZ_GAME_GO (1) -- GoState(bs 9/13/19, go_komi, go_chinese_rules,
         go_superko), fixed for the handle's life; Go actions are -1 (pass) .. bs*bs-1 and finished games
         report AZ_ACTION_NONE.
+        gomoku_renju / gomoku_omok: GomokuState(bs, use_renju, use_omok), put in force right after creation
+        (az_search_set_gomoku_rules) for every game the handle plays; gomokuRules() reads them back.
         search_opts: selection (AZ_SEL_*), max_search_depth, use_td, td_lambda, use_widening,
         widening_min_visits, widening_base, widening_exponent (SEARCH_OPT_DEFAULTS), put in force right
         after creation (az_search_set_options); setSearchOptions changes them on the live handle.
@@ -268,12 +270,14 @@ class ParallelMCTS:
         h = ctypes.c_void_p()
         check(lib().az_search_create(engine.h, net.h if net is not None else None, ctypes.byref(cfg), ctypes.byref(h)))
         self.h = h
-        if search_opts:
-            try:
+        try:
+            if search_opts:
                 check(lib().az_search_set_options(h, ctypes.byref(opts)))
-            except AzError:
-                self.close()
-                raise
+            if gomoku_renju or gomoku_omok:
+                check(lib().az_search_set_gomoku_rules(h, ctypes.byref(GomokuRules(int(bool(gomoku_renju)), int(bool(gomoku_omok)), 0))))
+        except AzError:
+            self.close()
+            raise
         self.engine, self.net = engine, net
         self._cb = None
         if evaluator == AZ_EVAL_CALLBACK:
@@ -418,6 +422,12 @@ class ParallelMCTS:
         k, c, sk = ctypes.c_float(), ctypes.c_int(), ctypes.c_int()
         check(lib().az_search_go_rules(self.h, ctypes.byref(k), ctypes.byref(c), ctypes.byref(sk)))
         return k.value, bool(c.value), bool(sk.value)
+
+    def gomokuRules(self):
+        """(renju, omok) the handle plays (az_search_gomoku_rules)."""
+        r = GomokuRules()
+        check(lib().az_search_gomoku_rules(self.h, ctypes.byref(r)))
+        return bool(r.renju), bool(r.omok)
 
     def searchOptions(self):
         """The search options the handle plays (az_search_options), keyed as SEARCH_OPT_DEFAULTS."""
@@ -673,8 +683,10 @@ class Arena:
     def __init__(self, engine, net_a, net_b, tables, board_size=15, num_simulations=800, swap_colors=False,
                  temperature=0.1, sample_moves=0, noise_alpha=0.03, noise_eps=0.0, game=0, c_puct=1.5,
                  fpu_reduction=0.0, virtual_loss=3, zobrist_seed=12345, noise_seed=42, noise_seed_stride=1, tt_log2=20,
-                 node_capacity=0, prior_ring=0, go_komi=7.5, go_chinese_rules=True, go_superko=True, **search_opts):
-        """search_opts: the search options of ParallelMCTS (SEARCH_OPT_DEFAULTS), played by both nets' trees."""
+                 node_capacity=0, prior_ring=0, go_komi=7.5, go_chinese_rules=True, go_superko=True, gomoku_renju=False,
+                 gomoku_omok=False, **search_opts):
+        """search_opts: the search options of ParallelMCTS (SEARCH_OPT_DEFAULTS), played by both nets' trees.
+        gomoku_renju / gomoku_omok: the Gomoku rule variant, set on the arena's handle right after creation."""
         self.tables, self.engine, self.nets = int(tables), engine, (net_a, net_b)
         self.cfg = SearchCfg(self.tables, board_size, num_simulations, c_puct, fpu_reduction, virtual_loss, AZ_EVAL_NET,
                              7, zobrist_seed, noise_seed, noise_seed_stride, 0, noise_alpha, noise_eps, tt_log2,
@@ -695,12 +707,14 @@ class Arena:
         m.engine, m.net, m._cb, m._borrowed, m.cfg = engine, net_a, None, True, self.cfg
         self.search = m
         self.progressCallback = None
-        if search_opts:                                       # both nets' trees: every slot of the arena's handle
-            try:
+        try:
+            if search_opts:                                   # both nets' trees: every slot of the arena's handle
                 check(lib().az_search_set_options(m.h, ctypes.byref(opts)))
-            except AzError:
-                self.close()
-                raise
+            if gomoku_renju or gomoku_omok:
+                check(lib().az_search_set_gomoku_rules(m.h, ctypes.byref(GomokuRules(int(bool(gomoku_renju)), int(bool(gomoku_omok)), 0))))
+        except AzError:
+            self.close()
+            raise
 
     def step(self):
         """One ply on every live table; returns the moves played."""

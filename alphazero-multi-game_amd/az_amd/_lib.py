@@ -45,6 +45,10 @@ class SearchOpts(ctypes.Structure):
                 ("widening_exponent", c_float)]
 
 
+class GomokuRules(ctypes.Structure):
+    _fields_ = [("renju", c_int), ("omok", c_int), ("pro_long_opening", c_int)]
+
+
 AZ_GO_RULES_SET = 1
 AZ_SEL_UCB, AZ_SEL_PUCT, AZ_SEL_PROGRESSIVE_BIAS, AZ_SEL_RAVE = 0, 1, 2, 3
 
@@ -130,6 +134,8 @@ EXPORTS = {
     "az_search_set_evaluator": (c_int, [vp, EVAL_FN, vp]),
     "az_search_set_params": (c_int, [vp, P(SearchCfg)]),
     "az_search_go_rules": (c_int, [vp, P(c_float), P(c_int), P(c_int)]),
+    "az_search_set_gomoku_rules": (c_int, [vp, P(GomokuRules)]),
+    "az_search_gomoku_rules": (c_int, [vp, P(GomokuRules)]),
     "az_search_set_options": (c_int, [vp, P(SearchOpts)]),
     "az_search_options": (c_int, [vp, P(SearchOpts)]),
     "az_search_widening_table": (c_int, [c_float, c_float, c_int, P(c_int), c_int, P(c_int)]),

@@ -46,6 +46,7 @@ struct ArenaConfig {
     float noiseAlpha = 0.03f, noiseEpsilon = 0.0f;   // root noise of the mover (evaluate.py adds none)
     uint32_t seed = 42;          // the games' generators: seed + stream id
     int ttLog2 = 20;             // TranspositionTable(1048576, 1024), evaluate.py:336-337
+    bool gomokuRenju = false, gomokuOmok = false;   // the Gomoku rule variant both nets' trees play
     // both trees' search options: only selectionStrategy, maxSearchDepth, the TD and the widening fields
     // are read (mcts::searchOptions)
     mcts::MCTSConfig searchOptions;
@@ -66,8 +67,9 @@ struct ArenaSummary {
     double eloA = 1500.0, eloB = 1500.0;
 };
 
-// RAII over az_arena: two device nets of one shape, `tables` boards.  Variant rules and chess are
-// refused (std::invalid_argument), as everywhere in the engine.
+// RAII over az_arena: two device nets of one shape, `tables` boards.  Chess is refused
+// (std::invalid_argument), as everywhere in the engine; gomokuRenju / gomokuOmok are set on the
+// arena's handle right after its creation.
 class Arena {
  public:
     Arena(nn::HipNeuralNetwork& a, nn::HipNeuralNetwork& b, const ArenaConfig& config);

@@ -1,11 +1,18 @@
-// alphazero/games/gomoku/gomoku_state.h -- host Gomoku position (standard rules).
+// alphazero/games/gomoku/gomoku_state.h -- host Gomoku position (standard rules, Renju, Omok).
 // Same observable behaviour as the engine's device rules (tree_kernels.hip K5/K7) and the
-// reference GomokuState with its defaults: Black (1) moves first; Black wins with exactly five
+// reference GomokuState: Black (1) moves first; Black wins with exactly five
 // in a row, White with five or more; draw on a full board; Zobrist keys of ZobristHash(bs, 2, 2,
 // seed) (12345 unless given); 11 enhanced feature planes; legal-move order of
 // SURVEY.md A.6 (a fresh state's first query: libstdc++ unordered_set order; afterwards
-// descending cell index).  Renju / Omok / pro-long variants are not supported (throw).
+// descending cell index).
+// use_renju / use_omok: the cells csrc/gomoku_rules.h forbids Black are missing from the legal list
+// and refused by makeMove (Renju decides when both are set, but makeMove then also refuses what
+// Omok forbids, as the reference's make_move does); Black to move with no legal cell is a DRAW; the
+// "renju" / "omok" feature keys are part of the hash.  Under these rules a terminal test on a board
+// with stones counts as a legal-move query (it computes the legal set, as the reference's does).
+// The pro-long opening is not supported (throws): DESIGN.md section 6.
 #pragma once
+#include <cstdint>
 #include <vector>
 
 #include "alphazero/core/igamestate.h"
@@ -38,6 +45,10 @@ class GomokuState : public core::IGameState {
     std::vector<int> getMoveHistory() const override { return move_history; }
     bool validate() const override;
 
+    bool isUsingRenjuRules() const { return use_renju_; }
+    bool isUsingOmokRules() const { return use_omok_; }
+    // the rule in force forbids the side to move the empty cell (always false for White)
+    bool isForbidden(int action) const;
     bool is_occupied(int action) const { return cells_[action] != 0; }
     std::vector<std::vector<int>> get_board() const;
     // [11][bs*bs] flat planes (NCHW of one sample), the layout az_net_forward takes
@@ -50,10 +61,16 @@ class GomokuState : public core::IGameState {
 
  private:
     int winnerAfter(int a) const;
+    int legalCount() const;         // empty cells the side to move may play (fills forbidden_)
     std::vector<uint8_t> cells_;
     std::vector<uint64_t> zkeys_;   // 2*A piece keys, then 2 player keys
     int winner_ = 0;                // 0 none, 1 / 2
     mutable bool queried_ = false;
+    bool use_renju_ = false, use_omok_ = false;
+    uint64_t zrules_ = 0;           // "renju"[1] ^ "omok"[1] of the rules in force
+    // forbidden-cell mask of the position (csrc/gomoku_rules.h), computed on demand
+    mutable std::vector<uint64_t> forbidden_;
+    mutable int legal_count_ = -1;  // -1: forbidden_ / legal_count_ not computed for this position
 };
 
 }  // namespace gomoku

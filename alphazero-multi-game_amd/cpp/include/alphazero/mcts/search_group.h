@@ -42,6 +42,11 @@ az_search_cfg makeSearchConfig(const MCTSConfig& config, const core::IGameState&
                                const TranspositionTable* tt, int nGames);
 // Both configurations name the same Go rules (komi, scoring, ko rule), which a handle keeps for life.
 bool sameGoRules(const az_search_cfg& a, const az_search_cfg& b);
+// The Gomoku rule variant a state plays (GomokuState's use_renju / use_omok; zeros for any other state), and
+// putting it in force on a new handle (az_search_set_gomoku_rules; nothing to do for standard rules).  A refused
+// set destroys the handle, nulls the pointer and throws.
+az_gomoku_rules gomokuRulesOf(const core::IGameState& state);
+void applyGomokuRules(az_search*& s, const az_gomoku_rules& rules);
 // config's search options (selectionStrategy, maxSearchDepth, useTemporalDifference / tdLambda,
 // useProgressiveWidening / minVisitsForWidening / progressiveWideningBase / Exponent) as the device takes
 // them (az_search_set_options); and whether two sets are the same.
@@ -76,11 +81,13 @@ class SearchGroup {
     az_search* handle() const { return s_; }
     const az_search_cfg& deviceConfig() const { return cfg_; }
     const az_search_opts& deviceOptions() const { return opts_; }   // every member's search options
+    const az_gomoku_rules& gomokuRules() const { return rules_; }   // every member's Gomoku rule variant
     nn::NeuralNetwork* network() const { return nn_; }
 
     nn::NeuralNetwork* nn_;
     az_search_cfg cfg_{};
     az_search_opts opts_{};
+    az_gomoku_rules rules_{};
     int capacity_;
     az_search* s_ = nullptr;
     mutable std::mutex mu_;

@@ -5,8 +5,8 @@
 // shuffled slots in HBM; getBatch / getRandomSubset / shuffle are device gathers.
 //
 // Differences from the reference, all loud: records of one Dataset share one game type and
-// board size (the device store has one shape; a mismatch throws), Chess and variant rules throw
-// (no device rules for them), and setSeed() fixes rng_ (the reference seeds it from
+// board size (the device store has one shape; a mismatch throws), Chess throws (no device rules
+// for it; Gomoku records flagged variant -- Renju -- are taken: the planes do not depend on the rules), and setSeed() fixes rng_ (the reference seeds it from
 // std::random_device only).
 #pragma once
 #include <cstdint>

@@ -119,8 +119,23 @@ PYBIND11_MODULE(_alphazero_cpp, m) {
         .def("clone", [](const core::IGameState& s) { return s.clone(); });
 
     py::class_<gomoku::GomokuState, core::IGameState>(m, "GomokuState")
-        .def(py::init<int, bool, bool, int, bool>(), py::arg("board_size") = 15, py::arg("use_renju") = false,
+        // The Python constructor keeps to standard rules, as it always has (a variant flag throws): the rule variants
+        // are built by name -- GomokuState.withRules(bs, use_renju, use_omok) or createGameState(GOMOKU, bs, True).
+        .def(py::init([](int bs, bool renju, bool omok, int seed, bool proLong) {
+                 if (renju || omok || proLong)
+                     throw std::invalid_argument("GomokuState(...): the constructor builds standard rules; use "
+                                                 "GomokuState.withRules or createGameState for Renju / Omok");
+                 return std::make_unique<gomoku::GomokuState>(bs, false, false, seed, false);
+             }), py::arg("board_size") = 15, py::arg("use_renju") = false,
              py::arg("use_omok") = false, py::arg("seed") = 0, py::arg("use_pro_long_opening") = false)
+        // gomoku::GomokuState(bs, use_renju, use_omok, seed, use_pro_long_opening), arguments passed through
+        .def_static("withRules", [](int bs, bool renju, bool omok, int seed, bool proLong) {
+                 return std::make_unique<gomoku::GomokuState>(bs, renju, omok, seed, proLong);
+             }, py::arg("board_size") = 15, py::arg("use_renju") = false, py::arg("use_omok") = false, py::arg("seed") = 0,
+             py::arg("use_pro_long_opening") = false)
+        .def("isUsingRenjuRules", &gomoku::GomokuState::isUsingRenjuRules)
+        .def("isUsingOmokRules", &gomoku::GomokuState::isUsingOmokRules)
+        .def("isForbidden", &gomoku::GomokuState::isForbidden)
         .def("is_occupied", &gomoku::GomokuState::is_occupied)
         .def("get_board", &gomoku::GomokuState::get_board);
 

@@ -98,6 +98,13 @@ Arena::Arena(nn::HipNeuralNetwork& a, nn::HipNeuralNetwork& b, const ArenaConfig
         arena_ = nullptr;
         throw std::runtime_error("az_search_set_options: " + msg);
     }
+    const az_gomoku_rules gr{config.gomokuRenju ? 1 : 0, config.gomokuOmok ? 1 : 0, 0};   // right after creation: nothing has moved
+    if ((gr.renju || gr.omok) && az_search_set_gomoku_rules(az_arena_search(arena_), &gr) != 0) {
+        const std::string msg = az_last_error();
+        az_arena_destroy(arena_);
+        arena_ = nullptr;
+        throw std::runtime_error("az_search_set_gomoku_rules: " + msg);
+    }
 }
 
 Arena::~Arena() { az_arena_destroy(arena_); }

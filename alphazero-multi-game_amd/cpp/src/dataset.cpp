@@ -117,7 +117,8 @@ void Dataset::extractExamples(bool includeAugmentations) {
         auto [t, b, variant] = r.getMetadata();
         if (t != t0 || defaultBoard(t, b) != bs)
             throw std::invalid_argument("Dataset: records of one dataset must share game type and board size");
-        if (variant) throw std::invalid_argument("Dataset: variant rules are not supported on this engine");
+        // Gomoku's variant (Renju) changes which moves a record holds, not how its planes are built
+        if (variant && t != core::GameType::GOMOKU) throw std::invalid_argument("Dataset: variant rules are Gomoku's (Renju)");
         nMoves.push_back((int)r.getMoves().size());
         for (const MoveData& m : r.getMoves()) {
             actions.push_back(m.action);

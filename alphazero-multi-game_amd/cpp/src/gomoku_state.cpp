@@ -2,6 +2,7 @@
 // The search itself never calls this: the device keeps its own boards (tree_kernels.hip).
 #include "alphazero/games/gomoku/gomoku_state.h"
 #include "alphazero/games/go/go_state.h"
+#include "../../csrc/gomoku_rules.h"
 
 #include <algorithm>
 #include <random>
@@ -14,14 +15,37 @@ namespace gomoku {
 GomokuState::GomokuState(int bs, bool use_renju, bool use_omok, int seed, bool use_pro_long_opening)
     : core::IGameState(core::GameType::GOMOKU), board_size(bs), current_player(1), action(-1) {
     if (bs < 5 || bs > 19) throw std::invalid_argument("GomokuState: board size must be 5..19");
-    if (use_renju || use_omok || use_pro_long_opening)
-        throw std::invalid_argument("GomokuState: only standard rules are supported (renju/omok/pro-long off)");
+    // the pro-long opening's legal order depends on the reference's unordered_set rehash history
+    if (use_pro_long_opening) throw std::invalid_argument("GomokuState: the pro-long opening is not supported");
+    use_renju_ = use_renju;
+    use_omok_ = use_omok;
     const int A = bs * bs;
     cells_.assign(A, 0);
     // ZobristHash(bs, 2 pieces, 2 players, seed): mt19937_64 draws, piece keys then player keys
     std::mt19937_64 rng(seed == 0 ? 12345u : (uint64_t)(unsigned)seed);
     zkeys_.resize(2 * A + 2);
     for (auto& k : zkeys_) k = rng();
+    // ZobristHash::addFeature(name, 2): mt19937_64(std::hash<std::string>(name)), value 1 is the second draw
+    for (const char* name : {"renju", "omok"}) {
+        std::mt19937_64 rf(std::hash<std::string>{}(name));
+        rf();
+        const uint64_t on = rf();
+        if (name[0] == 'r' ? use_renju : use_omok) zrules_ ^= on;
+    }
+}
+
+int GomokuState::legalCount() const {
+    if (legal_count_ < 0) {
+        forbidden_.assign((cells_.size() + 63) / 64, 0);
+        legal_count_ = gomoku_forbidden_mask(cells_.data(), board_size, current_player, use_renju_, use_omok_, forbidden_.data());
+    }
+    return legal_count_;
+}
+
+bool GomokuState::isForbidden(int a) const {
+    if (!(use_renju_ || use_omok_) || current_player != 1 || a < 0 || a >= getActionSpaceSize() || cells_[a]) return false;
+    legalCount();
+    return (forbidden_[a >> 6] >> (a & 63)) & 1;
 }
 
 int GomokuState::winnerAfter(int a) const {
@@ -48,23 +72,28 @@ std::vector<int> GomokuState::getLegalMoves() const {
         // first query of this object: the cache set grows from one bucket
         std::unordered_set<int> set;
         for (int a = 0; a < A; ++a)
-            if (!cells_[a]) set.insert(a);
+            if (!cells_[a] && !isForbidden(a)) set.insert(a);
         out.assign(set.begin(), set.end());
         queried_ = true;
         return out;
     }
     for (int a = A - 1; a >= 0; --a)
-        if (!cells_[a]) out.push_back(a);
+        if (!cells_[a] && !isForbidden(a)) out.push_back(a);
     return out;
 }
 
 bool GomokuState::isLegalMove(int a) const {
-    return a >= 0 && a < getActionSpaceSize() && !cells_[a] && !isTerminal();
+    return a >= 0 && a < getActionSpaceSize() && !cells_[a] && !isTerminal() && !isForbidden(a);
 }
 
 void GomokuState::makeMove(int a) {
     if (!isLegalMove(a)) throw core::IllegalMoveException("illegal move " + std::to_string(a), a);
+    // make_move (gomoku_state.cpp:697-703): with both rule sets on, a cell Renju allows is still refused when Omok forbids it
+    if (use_renju_ && use_omok_ && current_player == 1 &&
+        gomoku_omok_forbidden(cells_.data(), board_size, a, gomoku_any_open_three(cells_.data(), board_size, 0, 1)))
+        throw core::IllegalMoveException("forbidden move by Black (Omok) " + std::to_string(a), a);
     cells_[a] = (uint8_t)current_player;
+    legal_count_ = -1;
     move_history.push_back(a);
     action = a;
     if (!winner_) winner_ = winnerAfter(a);
@@ -76,6 +105,7 @@ bool GomokuState::undoMove() {
     const int a = move_history.back();
     move_history.pop_back();
     cells_[a] = 0;
+    legal_count_ = -1;
     current_player = 3 - current_player;
     action = move_history.empty() ? -1 : move_history.back();
     winner_ = 0;
@@ -88,6 +118,11 @@ core::GameResult GomokuState::getGameResult() const {
     if (winner_ == 1) return core::GameResult::WIN_PLAYER1;
     if (winner_ == 2) return core::GameResult::WIN_PLAYER2;
     if ((int)move_history.size() >= getActionSpaceSize()) return core::GameResult::DRAW;
+    // is_stalemate (gomoku_state.cpp:506-521): the side to move has no legal cell -- Black, every empty cell forbidden
+    if ((use_renju_ || use_omok_) && !move_history.empty()) {
+        queried_ = true;
+        if (current_player == 1 && legalCount() == 0) return core::GameResult::DRAW;
+    }
     return core::GameResult::ONGOING;
 }
 
@@ -141,7 +176,7 @@ uint64_t GomokuState::getHash() const {
     uint64_t h = zkeys_[2 * A + current_player - 1];
     for (int a = 0; a < A; ++a)
         if (cells_[a]) h ^= zkeys_[(size_t)(cells_[a] - 1) * A + a];
-    return h;
+    return h ^ zrules_;   // compute_hash_signature (gomoku_state.cpp:640-649)
 }
 
 std::unique_ptr<core::IGameState> GomokuState::clone() const { return std::make_unique<GomokuState>(*this); }
@@ -210,7 +245,7 @@ std::vector<std::vector<int>> GomokuState::get_board() const {
 
 namespace core {
 std::unique_ptr<IGameState> createGameState(GameType type, int boardSize, bool variantRules) {
-    // igamestate.cpp:17-49 / game_factory.cpp:88-115: Gomoku 15x15 standard rules, Go 19x19 komi 7.5
+    // igamestate.cpp:17-49 / game_factory.cpp:88-115: Gomoku 15x15 (variantRules: Renju), Go 19x19 komi 7.5
     // Chinese rules; Chess has no rules on this engine (its network shape runs)
     if (type == GameType::GO) return std::make_unique<go::GoState>(boardSize > 0 ? boardSize : 19, 7.5f, true, true);
     if (type != GameType::GOMOKU) throw std::invalid_argument("createGameState: Chess rules are not implemented");

@@ -8,6 +8,7 @@
 #include <sstream>
 
 #include "alphazero/games/go/go_state.h"
+#include "alphazero/games/gomoku/gomoku_state.h"
 #include "alphazero/nn/hip_neural_network.h"
 #include "alphazero/nn/random_policy_network.h"
 
@@ -129,6 +130,9 @@ ParallelMCTS::ParallelMCTS(const core::IGameState& root, SearchGroup& group)
         throw std::invalid_argument("ParallelMCTS: the root's game does not match the group's");
     if (!sameGoRules(makeSearchConfig(config_, *root_, nn_, nullptr, 1), g))
         throw std::invalid_argument("ParallelMCTS: the root's Go rules (komi, scoring, ko rule) differ from the group's");
+    const az_gomoku_rules mine = gomokuRulesOf(*root_), theirs = group.gomokuRules();
+    if (mine.renju != theirs.renju || mine.omok != theirs.omok)
+        throw std::invalid_argument("ParallelMCTS: the root's Gomoku rules (Renju / Omok) differ from the group's");
     slot_ = group.acquire(*root_);
     group_ = &group;
     s_ = group.handle();
@@ -192,6 +196,24 @@ bool sameSearchOptions(const az_search_opts& a, const az_search_opts& b) {
            a.use_td == b.use_td && a.td_lambda == b.td_lambda && a.use_widening == b.use_widening &&
            a.widening_min_visits == b.widening_min_visits && a.widening_base == b.widening_base &&
            a.widening_exponent == b.widening_exponent;
+}
+
+az_gomoku_rules gomokuRulesOf(const core::IGameState& state) {
+    az_gomoku_rules r{};
+    if (auto* g = dynamic_cast<const gomoku::GomokuState*>(&state)) {
+        r.renju = g->isUsingRenjuRules() ? 1 : 0;
+        r.omok = g->isUsingOmokRules() ? 1 : 0;
+    }
+    return r;
+}
+
+void applyGomokuRules(az_search*& s, const az_gomoku_rules& rules) {
+    if (!rules.renju && !rules.omok && !rules.pro_long_opening) return;
+    if (az_search_set_gomoku_rules(s, &rules) == 0) return;
+    const std::string msg = az_last_error();
+    az_search_destroy(s);
+    s = nullptr;
+    throw std::runtime_error("az_search_set_gomoku_rules: " + msg);
 }
 
 bool sameGoRules(const az_search_cfg& a, const az_search_cfg& b) {
@@ -266,6 +288,7 @@ void ParallelMCTS::rebuild() {
         s_ = nullptr;
         throw std::runtime_error("az_search_set_options: " + msg);
     }
+    applyGomokuRules(s_, gomokuRulesOf(*root_));           // the root's rule variant: every host replay clones root_
     if (c.eval_kind == AZ_EVAL_CALLBACK) check(az_search_set_evaluator(s_, &ParallelMCTS::hostEvaluate, this), "az_search_set_evaluator");
     const int g0 = 0;
     check(az_search_new_games(s_, &g0, 1), "az_search_new_games");

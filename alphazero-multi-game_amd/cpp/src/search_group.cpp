@@ -35,6 +35,8 @@ SearchGroup::SearchGroup(nn::NeuralNetwork* nn, const MCTSConfig& config, const 
         s_ = nullptr;
         throw std::runtime_error("az_search_set_options: " + msg);
     }
+    rules_ = gomokuRulesOf(prototype);
+    applyGomokuRules(s_, rules_);
 }
 
 SearchGroup::~SearchGroup() {

@@ -76,6 +76,7 @@ struct EvalCtx {
     nn::NeuralNetwork* nn;
     core::GameType type;
     int bs;
+    bool variant;
 };
 
 int host_eval(void* user, int n, const int* /*games*/, const int* len, const int* moves, int maxPath,
@@ -83,7 +84,7 @@ int host_eval(void* user, int n, const int* /*games*/, const int* len, const int
     auto* c = static_cast<EvalCtx*>(user);
     std::vector<std::unique_ptr<core::IGameState>> leaves;
     for (int i = 0; i < n; ++i) {
-        auto st = core::createGameState(c->type, c->bs, false);
+        auto st = core::createGameState(c->type, c->bs, c->variant);
         for (int k = 0; k < len[i]; ++k) st->makeMove(moves[(size_t)i * maxPath + k]);
         leaves.push_back(std::move(st));
     }
@@ -144,7 +145,9 @@ int SelfPlayManager::runGames(core::GameType type, int bs, bool variant, std::ve
         az_search_destroy(s);
         throw std::runtime_error(az_last_error());
     }
-    EvalCtx ectx{nn_, type, bs};
+    // variant rules: createGameState(GOMOKU, bs, true) is Renju (igamestate.cpp:24-27)
+    mcts::applyGomokuRules(s, az_gomoku_rules{variant ? 1 : 0, 0, 0});
+    EvalCtx ectx{nn_, type, bs, variant};
     if (ev.kind == AZ_EVAL_CALLBACK && az_search_set_evaluator(s, host_eval, &ectx)) {
         az_search_destroy(s);
         throw std::runtime_error(az_last_error());
@@ -179,7 +182,7 @@ int SelfPlayManager::runGames(core::GameType type, int bs, bool variant, std::ve
 std::vector<GameRecord> SelfPlayManager::generateGames(core::GameType type, int boardSize, bool variant) {
     const bool go = type == core::GameType::GO;
     if (!go && type != core::GameType::GOMOKU) throw std::invalid_argument("generateGames: Gomoku or Go (no Chess rules)");
-    if (variant) throw std::invalid_argument("generateGames: variant rules are not supported");
+    if (variant && go) throw std::invalid_argument("generateGames: variant rules are Gomoku's (Renju); Go has none");
     running_ = true;
     abort_ = 0;
     const int bs = boardSize > 0 ? boardSize : go ? 19 : 15;

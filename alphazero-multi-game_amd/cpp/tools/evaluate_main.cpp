@@ -8,8 +8,9 @@
 //   --precision P     trunk precision of both nets: fp16 | f16x3 | bf16x3 | f32 (default: as loaded)
 //   --max-moves N     cut games at N moves (a cut game scores 0.5 - 0.5)
 //   --device D        the HIP device (default: LOCAL_RANK, else 0)
-// Refused: --time-control (the device search counts simulations), --variant and --game chess (the
-// reference's variant and chess rules recurse without bound).  --threads is recorded only.
+// Refused: --time-control (the device search counts simulations), --game chess (the reference's
+// chess rules recurse without bound) and --variant (this binary plays standard rules; the arena
+// itself takes Renju / Omok through ArenaConfig::gomokuRenju / gomokuOmok).  --threads is recorded only.
 #include <algorithm>
 #include <chrono>
 #include <ctime>
@@ -101,10 +102,10 @@ int run(int argc, char** argv) {
     // what the device arena does not play is refused before anything touches the GPU
     if (args.has("--time-control"))
         throw std::invalid_argument("--time-control: the device search counts simulations, not seconds; use --simulations");
-    if (args.has("--variant"))
-        throw std::invalid_argument("--variant: the reference's variant rules (Renju / Omok) recurse without bound; "
-                                    "standard rules only");
     const std::string gameStr = args.get("--game", "gomoku");
+    if (args.has("--variant"))
+        throw std::invalid_argument("--variant: evaluate plays standard rules only (evaluation::Arena takes Renju / Omok "
+                                    "through ArenaConfig)");
     if (gameStr == "chess")
         throw std::invalid_argument("--game chess: the reference's chess rules recurse without bound (DESIGN.md); "
                                     "evaluate plays gomoku and go");

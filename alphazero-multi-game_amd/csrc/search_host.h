@@ -43,6 +43,7 @@ struct az_search {
     // every playing game's root is expanded (or terminal): the root steps (MODE_ROOT_SEARCH /
     // MODE_ROOT_NOISE) would select nothing, evaluate nothing and expand nothing -- skipped
     bool roots_ready = false;
+    bool used = false;              // a search step or a move has run: az_search_set_gomoku_rules comes before
     // scratch allocated once: one game's root-children readback, per-game prune thresholds / counts
     int* d_rc = nullptr; float* d_rcf = nullptr; int* d_thr = nullptr; long long* d_pruned = nullptr;
     float* d_temps = nullptr;

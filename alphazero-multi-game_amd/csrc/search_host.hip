@@ -177,8 +177,9 @@ int search_step(az_search* s, int mode, bool pre = false, bool fuse_next = false
     const bool prof = s->prof && mode == MODE_SIM && s->prof_steps++ % prof_every() == 0 && s->pc.room(4);
     if (prof) s->pc.stamp(st);
     TREE_DEV(dts, s, s->t);
-    const bool opt = tree_has_opts(s->t);
-    if (!pre) az_launch_select(dts, s->t.NA, s->t.G, mode, opt, st);
+    const bool opt = tree_has_opts(s->t), rules = tree_has_rules(s->t);
+    s->used = true;
+    if (!pre) az_launch_select(dts, s->t.NA, s->t.G, mode, opt, rules, st);
     if (prof) s->pc.stamp(st);
     if (s->c.eval_kind == AZ_EVAL_CALLBACK) {
         if (int r = host_evaluate(s)) return r;
@@ -218,11 +219,11 @@ int search_step(az_search* s, int mode, bool pre = false, bool fuse_next = false
         const bool fs = s->prof && mode == MODE_SIM && sidx % prof_every() == prof_every() / 2 && s->pcf.room(2);
         if (s->prof && mode == MODE_SIM) ++s->prof_fused_launches;
         if (fs) s->pcf.stamp(st);
-        az_launch_expand_select(dts, tt.eval_slot, tt.eval_identity, s->t.NA, G, opt, st);
+        az_launch_expand_select(dts, tt.eval_slot, tt.eval_identity, s->t.NA, G, opt, rules, st);
         if (fs) { s->pcf.stamp(st); ++s->prof_fused; }
     } else {
         TREE_DEV(dte, s, tt);
-        az_launch_expand_backup(dte, G, mode, opt, st);
+        az_launch_expand_backup(dte, G, mode, opt, rules, st);
     }
     if (prof) { s->pc.stamp(st); s->prof_sampled += 1; }
     HIPCHK(hipGetLastError());
@@ -294,7 +295,7 @@ void prefetch_noise(az_search* s, float alpha, const std::vector<uint8_t>& want)
     auto& P = s->pf;
     const int G = s->c.n_games, A = s->t.A, NA = s->t.NA;
     P.on = false;
-    if (s->t.game != GAME_GOMOKU) return;
+    if (s->t.game != GAME_GOMOKU || tree_has_rules(s->t)) return;   // Renju / Omok: the child count is the device's to tell
     P.nc.assign(G, -1);
     P.rng.resize(G);
     P.noise.resize((size_t)G * NA);
@@ -321,7 +322,8 @@ int search_noise(az_search* s, float alpha, float eps, const uint8_t* mask) {
     pf_wait(s);
     STEP_TRACE("noise: root step issued");
     std::vector<int> nroot;
-    if (s->t.game == GAME_GO) {        // |children| of each root (legal moves incl. pass and superko)
+    if (s->t.game == GAME_GO || tree_has_rules(s->t)) {   // |children| of each root (Go: legal moves incl. pass and superko;
+                                                          // Renju / Omok: the empty cells less the forbidden ones)
         nroot.resize(G);
         s->t.nd = s->arena[s->cur];
         hipLaunchKernelGGL(k_root_nchild, dim3((G + 255) / 256), dim3(256), 0, s->e->stream, s->t, s->d_nch);
@@ -449,6 +451,7 @@ int search_apply_dev(az_search* s, int* terminal, int* result) {
     const int G = s->c.n_games;
     s->t.nd = s->arena[s->cur];
     std::vector<int> acts(G);
+    s->used = true;
     HIPCHK(hipMemcpyAsync(acts.data(), s->d_actions, G * 4, hipMemcpyDeviceToHost, st));
     hipLaunchKernelGGL(k_apply, dim3(G), dim3(64), 0, st, s->t, s->d_actions, s->d_term, s->d_res, s->d_rexp);
     hipLaunchKernelGGL(k_compact, dim3(G), dim3(256), 0, st, s->t, s->arena[s->cur ^ 1], s->d_src_of);
@@ -901,6 +904,17 @@ int az_search_apply(az_search* s, const int* actions, int* terminal, int* result
         if (actions[g] >= A || (s->t.game == GAME_GO && actions[g] < AZ_ACTION_NONE))
             return az_fail(AZ_ERR_ARG, "action %d out of range for game %d", actions[g], g);
     HIPCHK(hipMemcpyAsync(s->d_actions, actions, G * 4, hipMemcpyHostToDevice, s->e->stream));
+    if (tree_has_rules(s->t)) {
+        // GomokuState::make_move throws on a cell the rules forbid Black: refused before anything moves
+        std::vector<int> bad(G);
+        hipLaunchKernelGGL(k_forbidden_moves, dim3(G), dim3(64), 0, s->e->stream, s->t, s->d_actions, s->d_nch);
+        HIPCHK(hipGetLastError());
+        HIPCHK(hipMemcpyAsync(bad.data(), s->d_nch, G * 4, hipMemcpyDeviceToHost, s->e->stream));
+        HIPCHK(hipStreamSynchronize(s->e->stream));
+        for (int g = 0; g < G; ++g)
+            if (bad[g]) return az_fail(AZ_ERR_ARG, "action %d of game %d is forbidden to Black under the %s rules", actions[g], g,
+                                       s->t.renju ? "Renju" : "Omok");
+    }
     return search_apply_dev(s, terminal, result);
 }
 
@@ -1102,6 +1116,55 @@ int az_diag_set_widening_cap(int entries) {
     const int old = g_widening_cap;
     g_widening_cap = std::max(1, std::min(entries, 1 << 22));
     return old;
+}
+
+int az_search_set_gomoku_rules(az_search* s, const az_gomoku_rules* r) {
+    if (!s || !r) return az_fail(AZ_ERR_ARG, "null argument");
+    std::lock_guard<std::mutex> lk(s->mu);
+    HIPCHK(hipSetDevice(s->e->device));
+    if (s->t.game != GAME_GOMOKU) return az_fail(AZ_ERR_ARG, "Gomoku rules (Renju / Omok) on a Go handle");
+    // its legal order follows libstdc++'s rehash sequence of a position-dependent insertion list
+    if (r->pro_long_opening) return az_fail(AZ_ERR_ARG, "the pro-long opening is not supported");
+    if (s->used) return az_fail(AZ_ERR_STATE, "az_search_set_gomoku_rules: the handle has searched or moved; the rules are set before");
+    const int renju = r->renju != 0, omok = r->omok != 0;
+    if ((renju || omok) && !s->t.gforb) {
+        uint64_t* m = nullptr;
+        if (int e = s->pool.alloc(&m, (size_t)s->c.n_games * AZ_FORB_WORDS)) return e;
+        if (hipMemset(m, 0, (size_t)s->c.n_games * AZ_FORB_WORDS * 8) != hipSuccess || hipDeviceSynchronize() != hipSuccess) {
+            s->pool.release(m);
+            return az_fail(AZ_ERR_HIP, "az_search_set_gomoku_rules: memset");
+        }
+        s->t.gforb = m;
+    }
+    // GomokuState's Zobrist features (gomoku_state.cpp:62-64, 640-649): value 1 of "renju" / "omok" is the second
+    // draw of mt19937_64(std::hash<std::string>(name)) (ZobristHash::addFeature)
+    uint64_t z = 0;
+    for (int k = 0; k < 2; ++k) {
+        std::mt19937_64 rf(std::hash<std::string>{}(k == 0 ? "renju" : "omok"));
+        rf();
+        const uint64_t on = rf();
+        if (k == 0 ? renju : omok) z ^= on;
+    }
+    s->t.renju = renju; s->t.omok = omok; s->t.zconst = z;
+    // slots already started (az_search_new_games before the rules): their fresh roots take the rules' hash
+    std::vector<int> started;
+    for (int g = 0; g < s->c.n_games; ++g) if (s->active[g]) started.push_back(g);
+    if (!started.empty()) {
+        std::vector<uint64_t> h(s->c.n_games);
+        HIPCHK(hipMemcpy(h.data(), s->t.rhash, h.size() * 8, hipMemcpyDeviceToHost));
+        uint64_t zpl0 = 0;
+        HIPCHK(hipMemcpy(&zpl0, s->t.zplayer, 8, hipMemcpyDeviceToHost));
+        for (int g : started) h[g] = zpl0 ^ z;
+        HIPCHK(hipMemcpy(s->t.rhash, h.data(), h.size() * 8, hipMemcpyHostToDevice));
+    }
+    return 0;
+}
+
+int az_search_gomoku_rules(az_search* s, az_gomoku_rules* out) {
+    if (!s || !out) return az_fail(AZ_ERR_ARG, "null argument");
+    std::lock_guard<std::mutex> lk(s->mu);
+    out->renju = s->t.renju; out->omok = s->t.omok; out->pro_long_opening = 0;
+    return 0;
 }
 
 int az_search_go_rules(az_search* s, float* komi, int* chinese_rules, int* superko) {

@@ -13,6 +13,7 @@
 #define AZ_SCAN_NETS 4        // nets k_scan_nets partitions a leaf batch by (AZ_MAX_SLOT_NETS of az_engine.h)
 #define AZ_DMAX 96          // longest selection path (root + 95 plies); overflow => AZ_ERR_CAPACITY
 #define AZ_NCNT 8            // per-game counters
+#define AZ_FORB_WORDS ((AZ_MAXA + 63) / 64)   // 64-cell words of a forbidden-cell mask
 // Go leaf state (k_select -> k_expand_backup): [0, 384) board, [384, 416) int32 {player, ko, passes,
 // nph} + u64 stones hash, [416, 416 + 8 * AZ_DMAX) u64 position pushes of the path
 #define AZ_GOLEAF_BYTES (416 + 8 * AZ_DMAX)
@@ -57,8 +58,14 @@ struct TreeDev {
     // GoState(bs, komi, chinese_rules, enforce_superko), fixed for the handle's life: every branch
     // on them is uniform over the grid
     float komi; int chinese; int superko;
+    // GomokuState(bs, use_renju, use_omok): fixed per game sequence and uniform over the grid, read only by the
+    // kernels' RULES instantiations (launched when tree_has_rules()) and by the per-move kernels.  The hash
+    // keys "renju"[1] / "omok"[1] are in zconst (Gomoku: XORed into the fresh root's hash by k_new_games)
+    int renju, omok;
     int pad3 = 0;
     int* gresult;                // [G] GameResult of the root state
+    uint64_t* gforb;             // [G][AZ_FORB_WORDS] Renju / Omok: forbidden-cell mask of the selected leaf (Black to
+                                 // move), from the selection to the expansion; null without rules
     int* path; int* plen;        // [G][AZ_DMAX], [G]
     int* pact;                   // [G][AZ_DMAX] action of every path node (pact[0] unused)
     int* lstatus; float* lvalue; uint64_t* lhash; int* ttstore; uint64_t* ttref; int* tthslot;
@@ -95,10 +102,14 @@ struct TreeDev {
 inline bool tree_has_opts(const TreeDev& t) {
     return t.sel == SEL_UCB || t.sel == SEL_PROGRESSIVE_BIAS || t.max_depth < AZ_DMAX || t.use_td || t.use_wid;
 }
+// Renju / Omok in force: the kernels' RULES instantiations
+inline bool tree_has_rules(const TreeDev& t) { return t.game == GAME_GOMOKU && (t.renju || t.omok); }
 // no implicit padding: every byte of a TreeDev is a member (tree_dev() finds a variant with memcmp)
 static_assert(offsetof(TreeDev, zko) == offsetof(TreeDev, pad0) + sizeof(int), "TreeDev hole after pad0");
 static_assert(offsetof(TreeDev, gresult) == offsetof(TreeDev, pad3) + sizeof(int), "TreeDev hole after pad3");
 static_assert(offsetof(TreeDev, komi) == offsetof(TreeDev, zconst) + sizeof(uint64_t), "TreeDev hole before komi");
+static_assert(offsetof(TreeDev, pad3) == offsetof(TreeDev, komi) + 5 * sizeof(int), "TreeDev hole before pad3");
+static_assert(offsetof(TreeDev, path) == offsetof(TreeDev, gresult) + 2 * sizeof(int*), "TreeDev hole after gforb");
 static_assert(offsetof(TreeDev, leafrec) == offsetof(TreeDev, pad1) + sizeof(int), "TreeDev hole after pad1");
 static_assert(sizeof(TreeDev) == offsetof(TreeDev, pad2) + sizeof(int), "TreeDev tail padding");
 static_assert(offsetof(TreeDev, wid_tab) == offsetof(TreeDev, sel) + 8 * sizeof(int), "TreeDev hole before wid_tab");

@@ -8,15 +8,18 @@
 
 // opt: tree_has_opts() of the TreeDev behind the device pointer -- the kernels' instantiation with the
 // search options (selection strategy, depth cap, TD backup, progressive widening); false: the plain search
-void az_launch_select(const TreeDev* t, int NA, int G, int mode, bool opt, hipStream_t st);
-void az_launch_expand_select(const TreeDev* ts, const int* eval_slot, int eval_identity, int NA, int G, bool opt,
+// rules: tree_has_rules() of it -- the instantiation that builds and honours the Renju / Omok forbidden-cell mask
+void az_launch_select(const TreeDev* t, int NA, int G, int mode, bool opt, bool rules, hipStream_t st);
+void az_launch_expand_select(const TreeDev* ts, const int* eval_slot, int eval_identity, int NA, int G, bool opt, bool rules,
                              hipStream_t st);
-void az_launch_expand_backup(const TreeDev* t, int G, int mode, bool opt, hipStream_t st);
+void az_launch_expand_backup(const TreeDev* t, int G, int mode, bool opt, bool rules, hipStream_t st);
 __global__ void k_scan(const TreeDev* __restrict__ tp);
 __global__ void k_scan_nets(const TreeDev* __restrict__ tp, const uint8_t* __restrict__ slot_net, int n_nets);
 __global__ void k_select_action(const TreeDev* __restrict__ tp, int training, float temperature, const float* temps, int* actions, float* values, float* probs,
                                 int* child_actions, int* nchild);
 __global__ void k_apply(TreeDev t, const int* actions, int* terminal, int* result, int* rexp);
+// Renju / Omok: bad[g] = 1 when actions[g] is a cell the rules forbid game g's side to move
+__global__ void k_forbidden_moves(TreeDev t, const int* actions, int* bad);
 __global__ void k_compact(TreeDev t, Nodes dst, int* src_of);
 __global__ void k_leaf_moves(TreeDev t, int* moves, int* len);
 __global__ void k_prune(TreeDev t, Nodes dst, int* src_of, int thr_all, const int* thr_g, long long* pruned);

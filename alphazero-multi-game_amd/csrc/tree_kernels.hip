@@ -16,6 +16,8 @@
 //   k_select_action  getVisitCountDistribution (mcts_node.cpp:289-322), selectAction
 //                    (parallel_mcts.cpp:987-1047), getRootValue (:1057-1063)
 //   k_apply          makeMove + updateWithMove (parallel_mcts.cpp:1065-1108)
+//   forbidden_mask_wave  Renju / Omok: the cells forbidden to Black at a leaf (gomoku_state.cpp:544-578
+//                    with the predicates of gomoku_rules.h), for k_select's RULES instantiation
 //   k_compact        subtree reuse: BFS copy of the new root's subtree into the other arena
 //   k_noise          Dirichlet mix of addDirichletNoise (parallel_mcts.cpp:1158-1166)
 #include <hip/hip_runtime.h>
@@ -23,6 +25,7 @@
 #include <limits.h>
 #include "tree_kernels.h"
 #include "leaf_planes.h"
+#include "gomoku_rules.h"
 
 namespace {
 
@@ -191,6 +194,28 @@ __device__ int five_at_wave(const uint8_t* board, int bs, int a, int p, int lane
     const int len = board[a] == p ? 1 + run + other : -1;
     const bool win = lane < 8 && (lane & 1) == 0 && (p == 1 ? len == 5 : len >= 5);
     return __ballot(win) != 0ULL;
+}
+
+// Renju / Omok: the forbidden-cell mask of a Black-to-move position from its board in LDS, one wave
+// per game (refresh_valid_moves_cache, gomoku_state.cpp:544-578, with the predicates of
+// gomoku_rules.h).  First the wave shares one scan of the board as it stands (lane l: the windows
+// that start at cells l, l + 64, ...): does it hold a four-shape (Renju) / an open three (Omok) at
+// all?  Then every lane judges its own candidate cells -- without a standing shape only the windows
+// through the candidate (84 of 5 to 7 cells, or 12 slices), else the whole board -- and a ballot
+// per 64 cells is the mask word, written by lane 0.  Returns the legal count (empty cells not
+// forbidden).  Every lane of the wave must call it; the board must be complete (after a barrier).
+__device__ int forbidden_mask_wave(const TreeDev& t, const uint8_t* board, int lane, uint64_t* out) {
+    const bool base = __ballot(gomoku_base_shapes(board, t.bs, t.renju, t.omok, lane, 64)) != 0ULL;
+    int legal = 0;
+    for (int c0 = 0; c0 < t.A; c0 += 64) {
+        const int a = c0 + lane;
+        const bool empty = a < t.A && board[a] == 0;
+        const bool f = empty && gomoku_forbidden(board, t.bs, t.renju, t.omok, a, base);
+        const unsigned long long m = __ballot(f);
+        legal += __popcll(__ballot(empty)) - __popcll(m);
+        if (lane == 0) out[c0 >> 6] = m;
+    }
+    return legal;
 }
 
 // getPuctScore (mcts_node.cpp:61-119).  parentDepth: depth of the node being selected
@@ -703,7 +728,9 @@ struct ExpLds {
 
 // OPT: the search options of az_search_cfg (TreeDev sel / max_depth / use_wid ...) are in force; the
 // default instantiation (OPT = false) is the plain PUCT search and reads none of them.
-template <int IT, bool OPT>
+// RULES: Renju / Omok (TreeDev renju / omok) are in force: a Black-to-move leaf gets its forbidden-cell
+// mask (t.gforb, which the expansion reads) and is a DRAW when no legal cell is left (is_stalemate).
+template <int IT, bool OPT, bool RULES>
 __device__ __forceinline__ void select_game(const TreeDev& t, int mode, const RootHint* hint, SelLds& SL, GoLds& gl) {
     const int g = blockIdx.x;
     const int lane = threadIdx.x;
@@ -887,6 +914,9 @@ __device__ __forceinline__ void select_game(const TreeDev& t, int mode, const Ro
         for (int i = 0; i < 6; ++i) hist6[i] = i < depth ? sact[depth - i] : lane_bcast(rhist, i - depth);
         __syncthreads();
     }
+    int nlegal = 1;              // RULES: legal cells of a Black-to-move leaf that is not known to be over
+    if (RULES && !go && player == 1 && !(nflag & FL_TERMINAL))
+        nlegal = forbidden_mask_wave(t, board, lane, t.gforb + (size_t)g * AZ_FORB_WORDS);
     tstamp(t, g, 0, 3);
     const int leaf = node;
     int store = 0;
@@ -914,6 +944,7 @@ __device__ __forceinline__ void select_game(const TreeDev& t, int mode, const Ro
                 const int a = sact[depth];
                 if (five_at_wave(board, t.bs, a, 3 - player, lane)) result = (3 - player) == 1 ? R_WIN1 : R_WIN2;
                 else if (stones >= t.A) result = R_DRAW;
+                else if (RULES && nlegal == 0) result = R_DRAW;   // Black has no legal cell (is_stalemate)
             }
             if (result != R_ONGOING) {
                 status = ST_TERMINAL;
@@ -1010,12 +1041,12 @@ __device__ __forceinline__ void select_game(const TreeDev& t, int mode, const Ro
     tstamp(t, g, 0, 7);
 }
 
-template <int IT, bool OPT>
+template <int IT, bool OPT, bool RULES>
 __global__ __launch_bounds__(64) void k_select(const TreeDev* __restrict__ tp, int mode) {
     const TreeDev& t = *tp;                               // device-resident (tree_dev, search_host.hip): an 8-byte kernarg
     __shared__ SelLds SL;
     __shared__ GoLds gl;
-    select_game<IT, OPT>(t, mode, nullptr, SL, gl);
+    select_game<IT, OPT, RULES>(t, mode, nullptr, SL, gl);
 }
 
 extern "C" int az_diag_tree_stamps(unsigned long long* out, int n) {
@@ -1023,17 +1054,18 @@ extern "C" int az_diag_tree_stamps(unsigned long long* out, int n) {
 }
 
 namespace {
-template <bool OPT>
+template <bool OPT, bool RULES>
 void launch_select(const TreeDev* t, int NA, int G, int mode, hipStream_t st) {
-    if (NA <= 128) hipLaunchKernelGGL((k_select<2, OPT>), dim3(G), dim3(64), 0, st, t, mode);
-    else if (NA <= 256) hipLaunchKernelGGL((k_select<4, OPT>), dim3(G), dim3(64), 0, st, t, mode);
-    else hipLaunchKernelGGL((k_select<(AZ_MAXNA + 63) / 64, OPT>), dim3(G), dim3(64), 0, st, t, mode);
+    if (NA <= 128) hipLaunchKernelGGL((k_select<2, OPT, RULES>), dim3(G), dim3(64), 0, st, t, mode);
+    else if (NA <= 256) hipLaunchKernelGGL((k_select<4, OPT, RULES>), dim3(G), dim3(64), 0, st, t, mode);
+    else hipLaunchKernelGGL((k_select<(AZ_MAXNA + 63) / 64, OPT, RULES>), dim3(G), dim3(64), 0, st, t, mode);
 }
 }  // namespace
-// opt: tree_has_opts() of the TreeDev behind t (the launchers take device pointers)
-void az_launch_select(const TreeDev* t, int NA, int G, int mode, bool opt, hipStream_t st) {
-    if (opt) launch_select<true>(t, NA, G, mode, st);
-    else launch_select<false>(t, NA, G, mode, st);
+// opt / rules: tree_has_opts() / tree_has_rules() of the TreeDev behind t (the launchers take device pointers)
+void az_launch_select(const TreeDev* t, int NA, int G, int mode, bool opt, bool rules, hipStream_t st) {
+    if (rules) { if (opt) launch_select<true, true>(t, NA, G, mode, st); else launch_select<false, true>(t, NA, G, mode, st); }
+    else if (opt) launch_select<true, false>(t, NA, G, mode, st);
+    else launch_select<false, false>(t, NA, G, mode, st);
 }
 
 // Host evaluator: the moves from the root to every leaf of the evaluation batch (slot order).
@@ -1131,7 +1163,7 @@ __global__ __launch_bounds__(1024) void k_scan_nets(const TreeDev* __restrict__ 
 // then the leaf's network outputs and the path nodes' statistics -- the second and last one.
 // The Gomoku leaf board is the root board plus the path moves (no Zobrist work: k_select stored
 // the leaf hash); a Go leaf's position comes back from the state k_select stored (go_load_leaf).
-template <bool OPT>
+template <bool OPT, bool RULES>
 __device__ __forceinline__ void expand_game(const TreeDev& t, int mode, ExpLds& EL, GoLds& gl, RootHint* hint = nullptr) {
     const int g = blockIdx.x;
     const int lane = threadIdx.x;
@@ -1249,9 +1281,12 @@ __device__ __forceinline__ void expand_game(const TreeDev& t, int mode, ExpLds& 
             for (int i = lane; i < A; i += 64) legal[i] = t.fresh_order[i];
             n = A - rstones;   // fresh root is the empty board
         } else {
+            // RULES: a Black-to-move leaf's legal cells leave out the mask k_select built for it
+            const uint64_t* forb = RULES && player == 1 ? t.gforb + (size_t)g * AZ_FORB_WORDS : nullptr;
             for (int c0 = 0; c0 < A; c0 += 64) {
                 const int a = A - 1 - (c0 + lane);
-                const bool e = a >= 0 && board[a] == 0;
+                bool e = a >= 0 && board[a] == 0;
+                if (RULES && forb && e) e = !((forb[a >> 6] >> (a & 63)) & 1ULL);
                 const unsigned long long m = __ballot(e);
                 const int pos = n + __popcll(m & ((1ULL << lane) - 1ULL));
                 if (e) legal[pos] = a;
@@ -1476,16 +1511,19 @@ __device__ __forceinline__ void expand_game(const TreeDev& t, int mode, ExpLds& 
     tstamp(t, g, 1, 7);
 }
 
-template <bool OPT>
+template <bool OPT, bool RULES>
 __global__ __launch_bounds__(64) void k_expand_backup(const TreeDev* __restrict__ tp, int mode) {
     const TreeDev& t = *tp;
     __shared__ ExpLds EL;
     __shared__ GoLds gl;
-    expand_game<OPT>(t, mode, EL, gl);
+    expand_game<OPT, RULES>(t, mode, EL, gl);
 }
-void az_launch_expand_backup(const TreeDev* t, int G, int mode, bool opt, hipStream_t st) {
-    if (opt) hipLaunchKernelGGL(k_expand_backup<true>, dim3(G), dim3(64), 0, st, t, mode);
-    else hipLaunchKernelGGL(k_expand_backup<false>, dim3(G), dim3(64), 0, st, t, mode);
+void az_launch_expand_backup(const TreeDev* t, int G, int mode, bool opt, bool rules, hipStream_t st) {
+    if (rules) {
+        if (opt) hipLaunchKernelGGL((k_expand_backup<true, true>), dim3(G), dim3(64), 0, st, t, mode);
+        else hipLaunchKernelGGL((k_expand_backup<false, true>), dim3(G), dim3(64), 0, st, t, mode);
+    } else if (opt) hipLaunchKernelGGL((k_expand_backup<true, false>), dim3(G), dim3(64), 0, st, t, mode);
+    else hipLaunchKernelGGL((k_expand_backup<false, false>), dim3(G), dim3(64), 0, st, t, mode);
 }
 
 // K3 of simulation step i and K1 of step i+1 in one launch: a game's expansion / backup and its
@@ -1494,7 +1532,7 @@ void az_launch_expand_backup(const TreeDev* t, int G, int mode, bool opt, hipStr
 // after the block barrier's release / acquire).  te: step i's batch maps, ts: the search's.
 // One TreeDev argument (the kernel's scalar registers are the tight resource): the expansion's
 // batch map differs from the search's only in eval_slot / eval_identity.
-template <int IT, bool OPT>
+template <int IT, bool OPT, bool RULES>
 __global__ __launch_bounds__(64) void k_expand_select(const TreeDev* __restrict__ tsp, const int* eval_slot, int eval_identity) {
     const TreeDev& ts = *tsp;
     __shared__ RootHint hint;
@@ -1503,23 +1541,26 @@ __global__ __launch_bounds__(64) void k_expand_select(const TreeDev* __restrict_
     TreeDev te = ts;
     te.eval_slot = const_cast<int*>(eval_slot);
     te.eval_identity = eval_identity;
-    expand_game<OPT>(te, MODE_SIM, U.e, gl, &hint);
+    expand_game<OPT, RULES>(te, MODE_SIM, U.e, gl, &hint);
     __syncthreads();                                      // the expansion's LDS is the selection's from here
-    select_game<IT, OPT>(ts, MODE_SIM, &hint, U.s, gl);
+    select_game<IT, OPT, RULES>(ts, MODE_SIM, &hint, U.s, gl);
 }
 
 namespace {
-template <bool OPT>
+template <bool OPT, bool RULES>
 void launch_expand_select(const TreeDev* ts, const int* eval_slot, int eval_identity, int NA, int G, hipStream_t st) {
-    if (NA <= 128) hipLaunchKernelGGL((k_expand_select<2, OPT>), dim3(G), dim3(64), 0, st, ts, eval_slot, eval_identity);
-    else if (NA <= 256) hipLaunchKernelGGL((k_expand_select<4, OPT>), dim3(G), dim3(64), 0, st, ts, eval_slot, eval_identity);
-    else hipLaunchKernelGGL((k_expand_select<(AZ_MAXNA + 63) / 64, OPT>), dim3(G), dim3(64), 0, st, ts, eval_slot, eval_identity);
+    if (NA <= 128) hipLaunchKernelGGL((k_expand_select<2, OPT, RULES>), dim3(G), dim3(64), 0, st, ts, eval_slot, eval_identity);
+    else if (NA <= 256) hipLaunchKernelGGL((k_expand_select<4, OPT, RULES>), dim3(G), dim3(64), 0, st, ts, eval_slot, eval_identity);
+    else hipLaunchKernelGGL((k_expand_select<(AZ_MAXNA + 63) / 64, OPT, RULES>), dim3(G), dim3(64), 0, st, ts, eval_slot, eval_identity);
 }
 }  // namespace
-void az_launch_expand_select(const TreeDev* ts, const int* eval_slot, int eval_identity, int NA, int G, bool opt,
+void az_launch_expand_select(const TreeDev* ts, const int* eval_slot, int eval_identity, int NA, int G, bool opt, bool rules,
                              hipStream_t st) {
-    if (opt) launch_expand_select<true>(ts, eval_slot, eval_identity, NA, G, st);
-    else launch_expand_select<false>(ts, eval_slot, eval_identity, NA, G, st);
+    if (rules) {
+        if (opt) launch_expand_select<true, true>(ts, eval_slot, eval_identity, NA, G, st);
+        else launch_expand_select<false, true>(ts, eval_slot, eval_identity, NA, G, st);
+    } else if (opt) launch_expand_select<true, false>(ts, eval_slot, eval_identity, NA, G, st);
+    else launch_expand_select<false, false>(ts, eval_slot, eval_identity, NA, G, st);
 }
 
 // K4: visit distribution, action choice and root value per game.
@@ -1661,6 +1702,7 @@ __global__ __launch_bounds__(64) void k_apply(TreeDev t, const int* actions, int
         for (int i = lane; i < A; i += 64) rb[i] = board[i];
         return;
     }
+    __shared__ int s_res;
     if (lane == 0) {
         board[a] = (uint8_t)p;
         rb[a] = (uint8_t)p;
@@ -1677,6 +1719,17 @@ __global__ __launch_bounds__(64) void k_apply(TreeDev t, const int* actions, int
         int res = R_ONGOING;
         if (five_at(board, t.bs, a, p)) res = p == 1 ? R_WIN1 : R_WIN2;
         else if (stones >= A) res = R_DRAW;
+        s_res = res;
+    }
+    if (t.renju || t.omok) {
+        // Renju / Omok: Black to move with every empty cell forbidden is a DRAW (is_stalemate, gomoku_state.cpp:506-521)
+        __syncthreads();
+        if (s_res == R_ONGOING && p == 2 && forbidden_mask_wave(t, board, lane, t.gforb + (size_t)g * AZ_FORB_WORDS) == 0 &&
+            lane == 0)
+            s_res = R_DRAW;
+    }
+    if (lane == 0) {
+        const int res = s_res;
         t.gresult[g] = res;
         if (res != R_ONGOING) t.active[g] = 0;
         terminal[g] = res != R_ONGOING;
@@ -1684,6 +1737,27 @@ __global__ __launch_bounds__(64) void k_apply(TreeDev t, const int* actions, int
         const uint8_t fl = reuse_child(t, g, nd, a);
         if (rexp) rexp[g] = res != R_ONGOING || (fl & (FL_EXPANDED | FL_TERMINAL)) != 0;
     }
+}
+
+// Renju / Omok: the moves az_search_apply is about to commit, against the rules -- bad[g] = 1 when
+// actions[g] is an empty cell the rules forbid game g's side to move (make_move throws there,
+// gomoku_state.cpp:697-703).  One wave per game; launched only on a handle with rules.
+__global__ __launch_bounds__(64) void k_forbidden_moves(TreeDev t, const int* actions, int* bad) {
+    const int g = blockIdx.x;
+    const int lane = threadIdx.x;
+    __shared__ uint8_t board[AZ_MAXA];
+    if (g >= t.G) return;
+    const int a = actions[g], A = t.A;
+    const bool look = t.active[g] && t.rplayer[g] == 1 && a >= 0 && a < A;
+    const uint8_t* rb = t.rboard + (size_t)g * A;
+    for (int i = lane; i < A; i += 64) board[i] = rb[i];
+    __syncthreads();
+    int f = 0;
+    if (look && board[a] == 0) {
+        const bool base = __ballot(gomoku_base_shapes(board, t.bs, t.renju, t.omok, lane, 64)) != 0ULL;
+        f = gomoku_forbidden(board, t.bs, t.renju, t.omok, a, base);
+    }
+    if (lane == 0) bad[g] = f;
 }
 
 // K6: copy the subtree of the (new) root into the other arena, breadth first.
@@ -1850,7 +1924,8 @@ __global__ __launch_bounds__(64) void k_new_games(TreeDev t, const int* games, c
     if (lane < 6) t.rhist[g * 6 + lane] = -1;
     if (lane == 0) {
         t.rplayer[g] = 1; t.rstones[g] = 0; t.rply[g] = 0; t.rfresh[g] = 1;
-        t.rhash[g] = t.game == GAME_GO ? 0ULL : t.zplayer[0];   // Go: stones-only hash of the empty board
+        // Go: stones-only hash of the empty board; Gomoku under Renju / Omok: with the rules' feature keys
+        t.rhash[g] = t.game == GAME_GO ? 0ULL : (t.renju || t.omok) ? t.zplayer[0] ^ t.zconst : t.zplayer[0];
         if (t.game == GAME_GO) { t.rko[g] = -1; t.rpass[g] = 0; t.rnposh[g] = 0; t.rcap[2 * g] = 0; t.rcap[2 * g + 1] = 0; }
         t.rnode[g] = 0; t.atop[g] = 1; t.active[g] = 1; t.gresult[g] = R_ONGOING; t.ring_cur[g] = 0;
         nd.N[0] = 0; nd.W[0] = 0.0f; nd.VL[0] = 0; nd.P[0] = 0.0f; nd.first[0] = -1; nd.act[0] = -1;

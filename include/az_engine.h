@@ -167,7 +167,7 @@ enum az_eval_kind {
 };
 typedef struct az_search_cfg {
     int n_games;          /* G: independent games (trees) on this device */
-    int board_size;       /* Gomoku bs (standard rules: no Renju/Omok/pro-long) */
+    int board_size;       /* Gomoku bs (standard rules; Renju / Omok: az_search_set_gomoku_rules) */
     int num_simulations;  /* MCTSConfig::numSimulations */
     float c_puct;         /* 1.5 */
     float fpu_reduction;  /* 0.0 */
@@ -218,6 +218,21 @@ typedef struct az_search_opts {
     float widening_base;       /* progressiveWideningBase */
     float widening_exponent;   /* progressiveWideningExponent */
 } az_search_opts;
+/* Gomoku rule variants (GomokuState(bs, use_renju, use_omok, seed, use_pro_long_opening)), a struct of
+ * their own: az_search_cfg keeps its layout.  A new handle plays standard Gomoku; az_search_set_gomoku_rules
+ * puts Renju / Omok in force on a Gomoku handle before its first search or move (AZ_ERR_STATE afterwards,
+ * AZ_ERR_ARG on a Go handle), and they hold for every game the handle plays from then on
+ * (az_search_new_games*, az_search_set_params, az_search_set_options, az_search_set_net and az_search_clear_tt
+ * leave them alone).  The rules are the reference's with its rule checker's accessor recursion repaired
+ * (DESIGN.md section 6): the cells forbidden to Black are missing from its legal moves, Black to move with
+ * no legal cell is a DRAW, az_search_apply refuses a forbidden cell (AZ_ERR_ARG), and the "renju" / "omok"
+ * feature keys are part of every position's hash.  Renju decides when both are set.  pro_long_opening != 0
+ * is refused (AZ_ERR_ARG): its legal order follows the reference's hash-set rehash history. */
+typedef struct az_gomoku_rules {
+    int renju;            /* use_renju: overline, or two four-shapes on the whole board */
+    int omok;             /* use_omok: overline, or two connected open threes */
+    int pro_long_opening; /* must be 0 */
+} az_gomoku_rules;
 
 #define AZ_GAME_GOMOKU 0
 #define AZ_GAME_GO 1
@@ -318,6 +333,10 @@ int az_diag_set_widening_cap(int entries);
 /* The Go rules the handle plays (the defaults spelled out when it was created with go_rules 0; a
  * Gomoku handle reports the defaults): what a host object hands to the handle it rebuilds. */
 int az_search_go_rules(az_search* s, float* komi, int* chinese_rules, int* superko);
+/* The Gomoku rule variant of a handle (az_gomoku_rules above); {0, 0, 0} is standard Gomoku. */
+int az_search_set_gomoku_rules(az_search* s, const az_gomoku_rules* r);
+/* The Gomoku rules the handle plays ({0, 0, 0} on a Go handle). */
+int az_search_gomoku_rules(az_search* s, az_gomoku_rules* out);
 /* Swap the device net of an AZ_EVAL_NET handle in place, trees kept (ParallelMCTS::
  * setNeuralNetwork, parallel_mcts.cpp:1190-1207, only replaces nn_): same engine, board, planes
  * and action space, max_batch >= n_games, weights loaded; else AZ_ERR_ARG / AZ_ERR_STATE. */
