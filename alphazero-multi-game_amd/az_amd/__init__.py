@@ -18,7 +18,7 @@ from dataclasses import dataclass, field
 
 import numpy as np
 
-from ._lib import (AZ_GO_RULES_SET, GomokuRules, AZ_SEL_PROGRESSIVE_BIAS, AZ_SEL_PUCT, AZ_SEL_RAVE, AZ_SEL_UCB, SearchOpts, AZ_EVAL_CALLBACK, AZ_EVAL_HASH, AZ_EVAL_NET, AZ_EVAL_RANDOM, AZ_EVAL_UNIFORM, EVAL_FN, AZ_PREC_BF16, AZ_PREC_BF16X3, AZ_PREC_F16X3, AZ_PREC_F32, AZ_PREC_FP16, AzError,
+from ._lib import (AZ_GO_RULES_SET, AZ_MAX_LEAVES, GomokuRules, AZ_SEL_PROGRESSIVE_BIAS, AZ_SEL_PUCT, AZ_SEL_RAVE, AZ_SEL_UCB, SearchOpts, AZ_EVAL_CALLBACK, AZ_EVAL_HASH, AZ_EVAL_NET, AZ_EVAL_RANDOM, AZ_EVAL_UNIFORM, EVAL_FN, AZ_PREC_BF16, AZ_PREC_BF16X3, AZ_PREC_F16X3, AZ_PREC_F32, AZ_PREC_FP16, AzError,
                    ARENA_SINK, ArenaCfg, ArenaSummary, GAME_SINK, PROGRESS_FN, MoveRec as _lib_MoveRec, NetDesc, SearchCfg, SelfPlayCfg, check, lib)
 
 __all__ = ["Engine", "HipNeuralNetwork", "ParallelMCTS", "SelfPlayManager", "Arena", "ArenaGameRecord", "EloRating", "GameRecord", "MoveData", "AzError",
@@ -245,7 +245,7 @@ class ParallelMCTS:
                  virtual_loss=3, evaluator=AZ_EVAL_HASH, net=None, eval_seed=7, zobrist_seed=12345, noise_seed=42,
                  noise_seed_stride=0, use_dirichlet_each_search=False, dirichlet_alpha=0.03, dirichlet_eps=0.25,
                  tt_log2=20, node_capacity=0, prior_ring=0, game=0, callback=None, go_komi=7.5, go_chinese_rules=True,
-                 go_superko=True, gomoku_renju=False, gomoku_omok=False, **search_opts):
+                 go_superko=True, gomoku_renju=False, gomoku_omok=False, leaves=1, **search_opts):
         """game: AZ_GAME_GOMOKU (0) or AZ_GAME_GO (1) -- GoState(bs 9/13/19, go_komi, go_chinese_rules,
         go_superko), fixed for the handle's life; Go actions are -1 (pass) .. bs*bs-1 and finished games
         report AZ_ACTION_NONE.
@@ -254,6 +254,8 @@ class ParallelMCTS:
         search_opts: selection (AZ_SEL_*), max_search_depth, use_td, td_lambda, use_widening,
         widening_min_visits, widening_base, widening_exponent (SEARCH_OPT_DEFAULTS), put in force right
         after creation (az_search_set_options); setSearchOptions changes them on the live handle.
+        leaves: leaf parallelism K (az_search_set_leaves; setLeafParallelism changes it between searches): a
+        simulation step makes K descents per game and evaluates their leaves as one batch of up to n_games x K.
         evaluator=AZ_EVAL_CALLBACK: callback(games [n], moves: per leaf the moves from the empty board,
         planes [n][C][bs][bs]) -> (policy [n][NA] as NeuralNetwork::predict returns it, value [n])."""
         self.G = n_games
@@ -275,6 +277,8 @@ class ParallelMCTS:
                 check(lib().az_search_set_options(h, ctypes.byref(opts)))
             if gomoku_renju or gomoku_omok:
                 check(lib().az_search_set_gomoku_rules(h, ctypes.byref(GomokuRules(int(bool(gomoku_renju)), int(bool(gomoku_omok)), 0))))
+            if leaves != 1:
+                check(lib().az_search_set_leaves(h, int(leaves)))
         except AzError:
             self.close()
             raise
@@ -442,6 +446,16 @@ class ParallelMCTS:
         options named change, the others stay as they are."""
         opts = _search_opts_struct(dict(self.searchOptions(), **search_opts))
         check(lib().az_search_set_options(self.h, ctypes.byref(opts)))
+
+    def setLeafParallelism(self, leaves):
+        """K descents per game and simulation step, their leaves one evaluator batch (az_search_set_leaves);
+        between searches, trees kept."""
+        check(lib().az_search_set_leaves(self.h, int(leaves)))
+
+    def getLeafParallelism(self):
+        k = ctypes.c_int()
+        check(lib().az_search_leaves(self.h, ctypes.byref(k)))
+        return k.value
 
     def rootNode(self, game):
         N = ctypes.c_int()

@@ -51,6 +51,7 @@ class GomokuRules(ctypes.Structure):
 
 AZ_GO_RULES_SET = 1
 AZ_SEL_UCB, AZ_SEL_PUCT, AZ_SEL_PROGRESSIVE_BIAS, AZ_SEL_RAVE = 0, 1, 2, 3
+AZ_MAX_LEAVES = 32   # az_search_set_leaves: the largest leaf parallelism
 
 
 class SelfPlayCfg(ctypes.Structure):
@@ -138,6 +139,8 @@ EXPORTS = {
     "az_search_gomoku_rules": (c_int, [vp, P(GomokuRules)]),
     "az_search_set_options": (c_int, [vp, P(SearchOpts)]),
     "az_search_options": (c_int, [vp, P(SearchOpts)]),
+    "az_search_set_leaves": (c_int, [vp, c_int]),
+    "az_search_leaves": (c_int, [vp, P(c_int)]),
     "az_search_widening_table": (c_int, [c_float, c_float, c_int, P(c_int), c_int, P(c_int)]),
     "az_diag_set_widening_cap": (c_int, [c_int]),
     "az_search_root_node": (c_int, [vp, c_int, P(c_int), P(c_int), P(c_float)]),

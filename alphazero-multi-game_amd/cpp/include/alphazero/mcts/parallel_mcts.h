@@ -5,6 +5,11 @@
 // as the reference does: the deterministic rules (forced by setDeterministicMode and by
 // SelfPlayManager) or libstdc++ draws on rng_ (parallel_mcts.cpp:987-1047).  numThreads / batch
 // settings are accepted and ignored (the device runs one simulation per game per step, Mode S).
+// Intra-tree parallelism is a setting of its own, setLeafParallelism(K) (az_search_set_leaves): K
+// descents per simulation step kept apart by virtual loss, their leaves one evaluator batch -- the
+// reference's numThreads = K workers in one fixed interleaving.  numThreads is NOT mapped onto it:
+// that would silently change what existing callers play, and the reference's SelfPlayManager
+// searches with min(numThreads_, 1) anyway.
 // selectionStrategy, maxSearchDepth, useTemporalDifference / tdLambda and the progressive-widening
 // fields of MCTSConfig go down to the device search (az_search_set_options) at creation and through
 // the setters, which keep the tree.
@@ -109,6 +114,11 @@ class ParallelMCTS {
     void setNeuralNetwork(nn::NeuralNetwork* nn);
     void setTranspositionTable(TranspositionTable* tt);
     void setSelectionStrategy(MCTSNodeSelection s);
+    // Leaf parallelism K in 1 .. AZ_MAX_LEAVES between searches, the tree kept; refused (std::runtime_error
+    // with the engine's message) together with non-default search options, Renju / Omok or a host-callback
+    // evaluator.  A group member has the group's K: asking for another one throws std::invalid_argument.
+    void setLeafParallelism(int leaves);
+    int getLeafParallelism() const { return leaves_; }
     void setConfig(const MCTSConfig& config);
     void enableBatchedMCTS(bool enable) { config_.useBatchedMCTS = enable; }
     void setBatchSize(int b) { config_.batchSize = b; }
@@ -142,6 +152,7 @@ class ParallelMCTS {
     az_search* s_ = nullptr;
     SearchGroup* group_ = nullptr;   // member of a group: s_ is the group's handle, slot_ the game
     int slot_ = 0;
+    int leaves_ = 1;                 // leaf parallelism of s_ (a member: the group's)
     std::vector<uint8_t> slotMask() const;
     struct RootSelect {
         std::vector<float> probs;

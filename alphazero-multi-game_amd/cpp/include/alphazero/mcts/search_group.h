@@ -72,6 +72,10 @@ class SearchGroup {
     // shared handle) after the last run; a single-threaded caller pays one window per search.
     // 0: requests that arrive during a run are batched into the next one only.
     void setGatherMicros(int us);
+    // Leaf parallelism of the group's handle (az_search_set_leaves), every member's: between searches.
+    // A member that asks for another value throws, as it does for other search options.
+    void setLeafParallelism(int leaves);
+    int leafParallelism() const;
 
  private:
     friend class ParallelMCTS;
@@ -97,6 +101,7 @@ class SearchGroup {
     std::map<int, std::string> errors_;
     bool running_ = false;
     int gatherUs_ = 2000;
+    int leaves_ = 1;
     size_t searches_ = 0, runs_ = 0;
 };
 

@@ -69,6 +69,10 @@ class SelfPlayManager {
     void setDistributed(Distributed* d) { dist_ = d; }
     const JobStats& getJobStats() const { return job_; }
     void setConcurrentGames(int n) { slots_ = n; }
+    // Leaf parallelism of the run's device search (az_search_set_leaves): K descents per game and simulation
+    // step, one evaluator batch of up to slots x K leaves.  numThreads stays unmapped.
+    void setLeafParallelism(int leaves) { leaves_ = leaves; }
+    int getLeafParallelism() const { return leaves_; }
     void setMaxMoves(int n) { maxMoves_ = n; }
     void setSeeds(unsigned noiseSeed, int noiseSeedStride) { noiseSeed_ = noiseSeed; noiseStride_ = noiseSeedStride; }
     // Evaluation log (tests: a game replayed through the CPU oracle): every network evaluation of device
@@ -97,7 +101,7 @@ class SelfPlayManager {
     volatile int abort_ = 0;
     std::atomic<bool> running_{false};
     std::atomic<int> completed_{0}, totalMoves_{0};
-    int slots_ = 0, maxMoves_ = 0;
+    int slots_ = 0, maxMoves_ = 0, leaves_ = 1;
     bool batchSet_ = false;
     unsigned noiseSeed_ = 42;
     int noiseStride_ = 1;

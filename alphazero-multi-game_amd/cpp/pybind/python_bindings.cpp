@@ -339,7 +339,9 @@ PYBIND11_MODULE(_alphazero_cpp, m) {
         .def("members", &mcts::SearchGroup::members)
         .def("searches", &mcts::SearchGroup::searches)
         .def("deviceRuns", &mcts::SearchGroup::deviceRuns)
-        .def("setGatherMicros", &mcts::SearchGroup::setGatherMicros);
+        .def("setGatherMicros", &mcts::SearchGroup::setGatherMicros)
+        .def("set_leaf_parallelism", &mcts::SearchGroup::setLeafParallelism, py::arg("leaves"))
+        .def("get_leaf_parallelism", &mcts::SearchGroup::leafParallelism);
 
     py::class_<mcts::ParallelMCTS>(m, "ParallelMCTS")
         .def(py::init<const core::IGameState&, nn::NeuralNetwork*, mcts::TranspositionTable*, int, int, float, float, int>(),
@@ -382,6 +384,8 @@ PYBIND11_MODULE(_alphazero_cpp, m) {
         .def("setNeuralNetwork", &mcts::ParallelMCTS::setNeuralNetwork, py::keep_alive<1, 2>())
         .def("setTranspositionTable", &mcts::ParallelMCTS::setTranspositionTable, py::keep_alive<1, 2>())
         .def("setSelectionStrategy", &mcts::ParallelMCTS::setSelectionStrategy)
+        .def("set_leaf_parallelism", &mcts::ParallelMCTS::setLeafParallelism, py::arg("leaves"))
+        .def("get_leaf_parallelism", &mcts::ParallelMCTS::getLeafParallelism)
         .def("setConfig", &mcts::ParallelMCTS::setConfig)
         .def("enableBatchedMCTS", &mcts::ParallelMCTS::enableBatchedMCTS)
         .def("setBatchSize", &mcts::ParallelMCTS::setBatchSize)
@@ -584,6 +588,8 @@ PYBIND11_MODULE(_alphazero_cpp, m) {
         .def("getCompletedGamesCount", &selfplay::SelfPlayManager::getCompletedGamesCount)
         .def("getTotalMovesCount", &selfplay::SelfPlayManager::getTotalMovesCount)
         .def("setConcurrentGames", &selfplay::SelfPlayManager::setConcurrentGames)
+        .def("setLeafParallelism", &selfplay::SelfPlayManager::setLeafParallelism, py::arg("leaves"))
+        .def("getLeafParallelism", &selfplay::SelfPlayManager::getLeafParallelism)
         .def("setMaxMoves", &selfplay::SelfPlayManager::setMaxMoves)
         .def("setSeeds", &selfplay::SelfPlayManager::setSeeds)
         .def("setShard", &selfplay::SelfPlayManager::setShard)

@@ -130,6 +130,7 @@ ParallelMCTS::ParallelMCTS(const core::IGameState& root, SearchGroup& group)
         throw std::invalid_argument("ParallelMCTS: the root's game does not match the group's");
     if (!sameGoRules(makeSearchConfig(config_, *root_, nn_, nullptr, 1), g))
         throw std::invalid_argument("ParallelMCTS: the root's Go rules (komi, scoring, ko rule) differ from the group's");
+    leaves_ = group.leafParallelism();
     const az_gomoku_rules mine = gomokuRulesOf(*root_), theirs = group.gomokuRules();
     if (mine.renju != theirs.renju || mine.omok != theirs.omok)
         throw std::invalid_argument("ParallelMCTS: the root's Gomoku rules (Renju / Omok) differ from the group's");
@@ -256,6 +257,17 @@ void ParallelMCTS::applyConfig() {
     rebuild();
 }
 
+void ParallelMCTS::setLeafParallelism(int leaves) {
+    if (group_) {
+        if (leaves != group_->leafParallelism())
+            throw std::invalid_argument("ParallelMCTS: a group member's leaf parallelism is the group's (" +
+                                        std::to_string(group_->leafParallelism()) + "), not " + std::to_string(leaves));
+        return;
+    }
+    check(az_search_set_leaves(s_, leaves), "az_search_set_leaves");
+    leaves_ = leaves;
+}
+
 // parallel_mcts.h:180: config_.selectionStrategy = strategy, the tree kept (az_search_set_params)
 void ParallelMCTS::setSelectionStrategy(MCTSNodeSelection s) {
     const MCTSNodeSelection old = config_.selectionStrategy;
@@ -289,6 +301,13 @@ void ParallelMCTS::rebuild() {
         throw std::runtime_error("az_search_set_options: " + msg);
     }
     applyGomokuRules(s_, gomokuRulesOf(*root_));           // the root's rule variant: every host replay clones root_
+    if (leaves_ > 1 && az_search_set_leaves(s_, leaves_) != 0) {   // refused with these options / rules / evaluator
+        const std::string msg = az_last_error();
+        az_search_destroy(s_);
+        s_ = nullptr;
+        leaves_ = 1;
+        throw std::runtime_error("az_search_set_leaves: " + msg);
+    }
     if (c.eval_kind == AZ_EVAL_CALLBACK) check(az_search_set_evaluator(s_, &ParallelMCTS::hostEvaluate, this), "az_search_set_evaluator");
     const int g0 = 0;
     check(az_search_new_games(s_, &g0, 1), "az_search_new_games");

@@ -60,6 +60,18 @@ size_t SearchGroup::deviceRuns() const {
     return runs_;
 }
 
+void SearchGroup::setLeafParallelism(int leaves) {
+    std::unique_lock<std::mutex> lk(mu_);
+    cv_.wait(lk, [&] { return !running_; });          // between device searches
+    check(az_search_set_leaves(s_, leaves), "az_search_set_leaves");
+    leaves_ = leaves;
+}
+
+int SearchGroup::leafParallelism() const {
+    std::lock_guard<std::mutex> lk(mu_);
+    return leaves_;
+}
+
 void SearchGroup::setGatherMicros(int us) {
     std::lock_guard<std::mutex> lk(mu_);
     gatherUs_ = us > 0 ? us : 0;

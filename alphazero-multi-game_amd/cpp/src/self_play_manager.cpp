@@ -147,6 +147,10 @@ int SelfPlayManager::runGames(core::GameType type, int bs, bool variant, std::ve
     }
     // variant rules: createGameState(GOMOKU, bs, true) is Renju (igamestate.cpp:24-27)
     mcts::applyGomokuRules(s, az_gomoku_rules{variant ? 1 : 0, 0, 0});
+    if (leaves_ != 1 && az_search_set_leaves(s, leaves_)) {
+        az_search_destroy(s);
+        throw std::runtime_error(az_last_error());
+    }
     EvalCtx ectx{nn_, type, bs, variant};
     if (ev.kind == AZ_EVAL_CALLBACK && az_search_set_evaluator(s, host_eval, &ectx)) {
         az_search_destroy(s);

@@ -16,6 +16,8 @@
 //   --concurrent-games N   device game slots, at most --batch-size (the reference's batch: one leaf
 //                      per game slot per simulation step)
 //   --max-moves N      cut games at N moves
+//   --leaves K         leaf parallelism: K descents per game and simulation step, one network batch of up to
+//                      slots x K leaves (default 1; --threads stays recorded only)
 #include <algorithm>
 #include <chrono>
 #include <cstdlib>
@@ -81,7 +83,8 @@ void usage() {
                  "  --net-blocks B --net-channels F --seed S   random-init residual net without --model\n"
                  "  --precision P           fp16 | f16x3 | bf16x3 | f32\n"
                  "  --concurrent-games N    device game slots, at most --batch-size\n"
-                 "  --max-moves N           cut games at N moves\n";
+                 "  --max-moves N           cut games at N moves\n"
+                 "  --leaves K              leaf parallelism: K descents per game and step, one batch of slots x K (default 1)\n";
 }
 
 core::GameType gameTypeOf(const std::string& s) {
@@ -174,7 +177,7 @@ int run(int argc, char** argv) {
                 s.channels = netChannels;
                 s.blocks = netBlocks;
                 s.precision = AZ_PREC_F32;
-                s.maxBatch = std::max(batchSize, args.getInt("--concurrent-games", batchSize));
+                s.maxBatch = std::max(batchSize, args.getInt("--concurrent-games", batchSize)) * std::max(1, args.getInt("--leaves", 1));
                 auto h = std::make_unique<nn::HipNeuralNetwork>(s, device);
                 h->initRandom((uint64_t)args.getInt("--seed", 1234));
                 net = std::move(h);
@@ -219,6 +222,7 @@ int run(int argc, char** argv) {
     mgr.setBatchConfig(batchSize, batchTimeout);
     if (args.has("--concurrent-games")) mgr.setConcurrentGames(args.getInt("--concurrent-games", batchSize));
     if (args.has("--max-moves")) mgr.setMaxMoves(args.getInt("--max-moves", 0));
+    if (args.has("--leaves")) mgr.setLeafParallelism(args.getInt("--leaves", 1));
     mgr.setSaveGames(true, outputDir);
     mcts::MCTSConfig mc;
     mc.numThreads = numThreads;

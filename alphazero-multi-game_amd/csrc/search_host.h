@@ -23,6 +23,12 @@ struct az_search {
     int net_slots[AZ_MAX_SLOT_NETS] = {};   // slots assigned to each net: its forward's capacity
     uint8_t* d_slot_net = nullptr;          // [G]
     az_search_cfg c{};
+    // Leaf parallelism (az_search_set_leaves): a simulation step makes `leaves` descents per game before it
+    // completes any of them, and their leaves share one evaluator batch.  The per-step scratch of `t` (path, pact,
+    // pstat, plen, lstatus, lvalue, lhash, ttstore, ttref, tthslot, need_eval, eval_slot, eval_games, leafrec,
+    // goleaf) and the batch buffers (d_batch, d_logits, d_value, d_id) hold G * leaves rows, indexed by leaf
+    // slot g * leaves + j; the root steps run on rows 0 .. G-1 as they do at leaves = 1.
+    int leaves = 1;
     TreeDev t{};
     Nodes arena[2]{};
     int cur = 0;

@@ -68,7 +68,7 @@ int check_err(az_search* s) {
     HIPCHK(hipMemcpyAsync(&err, s->t.err, 4, hipMemcpyDeviceToHost, s->e->stream));
     if (s->net && s->c.eval_kind == AZ_EVAL_NET) HIPCHK(hipMemcpyAsync(&ovf, s->net->ovf, 4, hipMemcpyDeviceToHost, s->e->stream));
     HIPCHK(hipStreamSynchronize(s->e->stream));
-    if (err) return az_fail(AZ_ERR_CAPACITY, "device capacity exceeded (flags 0x%x: 1 node pool, 2 path, 4 prior ring, 32 widening table)", err);
+    if (err) return az_fail(AZ_ERR_CAPACITY, "device capacity exceeded (flags 0x%x: 1 node pool, 2 path, 4 prior ring, 8 leaf batch, 32 widening table)", err);
     if (int r = check_ovf(s->net, ovf)) return r;
     // per-slot nets: every other net's range guard (nets[0] is s->net, read above)
     for (int k = 1; k < s->n_nets; ++k) {
@@ -231,10 +231,53 @@ int search_step(az_search* s, int mode, bool pre = false, bool fuse_next = false
     return 0;
 }
 
+// One wave of a handle with leaves = K > 1: k <= K descents per game (k_wave_select), one evaluator batch over
+// the G * K leaf slots, the k completions per game in descent order (k_wave_expand).  The batch is the identity
+// when every game plays and the wave is full; the net runs on every leaf that may need it, and a forward whose
+// completion then finds a TT hit or an expanded leaf is dropped (not an evaluation: `evals` counts completions).
+int wave_step(az_search* s, int k) {
+    hipStream_t st = s->e->stream;
+    const int G = s->c.n_games, K = s->leaves, Q = G * K;
+    s->t.nd = s->arena[s->cur];
+    TREE_DEV(dts, s, s->t);
+    s->used = true;
+    az_launch_wave_select(dts, s->t.NA, G, K, k, st);
+    TreeDev tt = s->t;
+    if (s->c.eval_kind == AZ_EVAL_NET) {
+        bool identity = k == K && s->d_id != nullptr;
+        for (int g = 0; identity && g < G; ++g) identity = s->active[g] != 0;
+        if (identity) {
+            tt.eval_slot = s->d_id; tt.eval_games = s->d_id; tt.n_eval = s->d_id + Q; tt.eval_identity = 1;
+        } else {
+            hipLaunchKernelGGL(k_scan_leaves, dim3(1), dim3(1024), 0, st, dts, Q);
+        }
+        const bool in_place = net_input_path(s->net) != NET_IN_GEMM;
+        const LeafRecs lr{tt.leafrec, tt.eval_games, tt.game == GAME_GO, Q, identity ? 1 : 0};
+        if (!in_place) az_launch_rec_planes(tt.leafrec, s->d_batch, tt.eval_games, tt.n_eval, lr.go, tt.bs, Q, st);
+        const int r = in_place ? net_forward(s->net, nullptr, Q, tt.n_eval, s->d_logits, s->d_value, st, &lr)
+                               : net_forward(s->net, s->d_batch, Q, tt.n_eval, s->d_logits, s->d_value, st);
+        if (r) return r;
+    }
+    TREE_DEV(dte, s, tt);
+    az_launch_wave_expand(dte, G, K, k, st);
+    HIPCHK(hipGetLastError());
+    return 0;
+}
+
 // n simulation steps.  Step i's expansion and step i+1's selection share one launch
 // (k_expand_select) except around the profiled steps (their kernels are timed separately) and
 // with the host evaluator (which runs between the two).
+// leaves = K > 1: ceil(n / K) waves, the last one short when K does not divide n.
 int search_sims(az_search* s, int n) {
+    if (s->leaves > 1) {
+        for (int done = 0, w = 0; done < n; ++w) {
+            const int k = std::min(s->leaves, n - done);
+            if (int r = wave_step(s, k)) return r;
+            done += k;
+            if (g_sync_every > 0 && (w + 1) % g_sync_every == 0) HIPCHK(hipStreamSynchronize(s->e->stream));
+        }
+        return 0;
+    }
     const bool can_fuse = s->c.eval_kind != AZ_EVAL_CALLBACK;
     bool pre = false;
     for (int i = 0; i < n; ++i) {
@@ -967,6 +1010,8 @@ int az_search_set_net(az_search* s, az_net* net) {
     if (net->d.max_batch < s->c.n_games) return az_fail(AZ_ERR_ARG, "network max_batch < n_games");
     if (!net->loaded) return az_fail(AZ_ERR_STATE, "network weights not loaded");
     std::lock_guard<std::mutex> lk(s->mu);
+    if (net->d.max_batch < s->c.n_games * s->leaves)
+        return az_fail(AZ_ERR_ARG, "network max_batch %d < n_games %d x leaves %d", net->d.max_batch, s->c.n_games, s->leaves);
     s->net = net;
     s->n_nets = 0;   // back to one net for every slot (the region buffers stay: region 0 is the batch)
     return 0;
@@ -997,6 +1042,7 @@ int az_search_set_slot_nets(az_search* s, az_net* const* nets, int n_nets, const
         if (!net->loaded) return az_fail(AZ_ERR_STATE, "net %d: weights not loaded", k);
     }
     std::lock_guard<std::mutex> lk(s->mu);
+    if (s->leaves > 1) return az_fail(AZ_ERR_ARG, "per-slot nets on a handle with leaves = %d (leaf parallelism takes one net)", s->leaves);
     HIPCHK(hipSetDevice(s->e->device));
     hipStream_t st = s->e->stream;
     int* games = nullptr; int* n_eval = nullptr; float* logits = nullptr; float* value = nullptr; float* batch = nullptr;
@@ -1090,7 +1136,86 @@ int az_search_set_options(az_search* s, const az_search_opts* opts) {
     if (int r = check_search_opts(o)) return r;
     std::lock_guard<std::mutex> lk(s->mu);
     HIPCHK(hipSetDevice(s->e->device));
+    if (s->leaves > 1) {
+        TreeDev probe = s->t;
+        probe.sel = o.selection; probe.max_depth = o.max_search_depth; probe.use_td = o.use_td; probe.use_wid = o.use_widening;
+        if (tree_has_opts(probe))
+            return az_fail(AZ_ERR_ARG, "non-default search options on a handle with leaves = %d (set leaves = 1 first)", s->leaves);
+    }
     return apply_search_opts(s, o);
+}
+
+// Leaf parallelism: K descents per game and simulation step, one evaluator batch of up to n_games x K leaves.
+// Between searches; trees, tables, counters and generators are kept.  The per-step scratch and the batch buffers
+// are replaced by ones of n_games x K rows from the handle's pool; every check and allocation comes before the
+// handle changes.
+int az_search_set_leaves(az_search* s, int leaves) {
+    if (!s) return az_fail(AZ_ERR_ARG, "null search");
+    if (leaves < 1 || leaves > AZ_MAX_LEAVES) return az_fail(AZ_ERR_ARG, "leaves %d outside 1..%d", leaves, AZ_MAX_LEAVES);
+    std::lock_guard<std::mutex> lk(s->mu);
+    HIPCHK(hipSetDevice(s->e->device));
+    TreeDev& t = s->t;
+    const int G = s->c.n_games, K = leaves, A = t.A, NA = t.NA;
+    if (K > 1) {
+        if (s->c.eval_kind == AZ_EVAL_CALLBACK)
+            return az_fail(AZ_ERR_ARG, "leaves %d with AZ_EVAL_CALLBACK: the host evaluator takes leaves = 1", K);
+        if (tree_has_opts(t)) return az_fail(AZ_ERR_ARG, "leaves %d with non-default search options (az_search_set_options)", K);
+        if (tree_has_rules(t)) return az_fail(AZ_ERR_ARG, "leaves %d with the %s rules", K, t.renju ? "Renju" : "Omok");
+        if (s->n_nets > 0) return az_fail(AZ_ERR_ARG, "leaves %d with per-slot nets (%d nets)", K, s->n_nets);
+    }
+    if (s->c.eval_kind == AZ_EVAL_NET && s->net && s->net->d.max_batch < G * K)
+        return az_fail(AZ_ERR_ARG, "network max_batch %d < n_games %d x leaves %d = %d", s->net->d.max_batch, G, K, G * K);
+    if (K == s->leaves) return 0;
+    const size_t Q = (size_t)G * K, R = (size_t)std::max(1, s->regions) * Q;
+    const bool net = s->c.eval_kind == AZ_EVAL_NET, cb = s->c.eval_kind == AZ_EVAL_CALLBACK;
+    DevPool fresh;   // the new buffers, the handle's only once everything succeeded
+    int* path = nullptr; int* pact = nullptr; int4* pstat = nullptr; int* plen = nullptr; int* lstatus = nullptr;
+    float* lvalue = nullptr; uint64_t* lhash = nullptr; int* ttstore = nullptr; uint64_t* ttref = nullptr; int* tthslot = nullptr;
+    int* need_eval = nullptr; int* eval_slot = nullptr; int* eval_games = nullptr; uint8_t* leafrec = nullptr; uint8_t* goleaf = nullptr;
+    float* batch = nullptr; float* logits = nullptr; float* value = nullptr; int* id = nullptr;
+    int r = 0;
+#define FA(p, n) do { if (!r) r = fresh.alloc(&(p), (size_t)(n)); } while (0)
+    FA(path, Q * AZ_DMAX); FA(pact, Q * AZ_DMAX); FA(pstat, Q * AZ_DMAX); FA(plen, Q); FA(lstatus, Q); FA(lvalue, Q); FA(lhash, Q);
+    FA(ttstore, Q); FA(ttref, Q); FA(tthslot, Q); FA(need_eval, Q); FA(eval_slot, Q); FA(eval_games, R);
+    FA(leafrec, Q * AZ_REC_BYTES);
+    if (t.game == GAME_GO) FA(goleaf, Q * AZ_GOLEAF_BYTES);
+    if (net || cb) { FA(batch, R * A * 16); FA(logits, R * NA); FA(value, R); }
+    if (net) FA(id, Q + 1);
+#undef FA
+    if (r) return r;
+    hipError_t he = hipStreamSynchronize(s->e->stream);   // no queued kernel reads the old buffers
+    if (he == hipSuccess) he = hipMemset(lstatus, 0, Q * 4);
+    if (he == hipSuccess) he = hipMemset(need_eval, 0, Q * 4);
+    if (he == hipSuccess) he = hipMemset(eval_games, 0, R * 4);
+    if (he == hipSuccess) he = hipMemset(leafrec, 0, Q * AZ_REC_BYTES);
+    if (he == hipSuccess && id) {
+        std::vector<int> h(Q + 1);
+        for (size_t i = 0; i <= Q; ++i) h[i] = (int)i;
+        he = hipMemcpy(id, h.data(), (Q + 1) * 4, hipMemcpyHostToDevice);
+    }
+    if (he == hipSuccess) he = hipDeviceSynchronize();
+    if (he != hipSuccess) return az_fail(AZ_ERR_HIP, "az_search_set_leaves: %s", hipGetErrorString(he));
+    for (void* p : {(void*)t.path, (void*)t.pact, (void*)t.pstat, (void*)t.plen, (void*)t.lstatus, (void*)t.lvalue, (void*)t.lhash,
+                    (void*)t.ttstore, (void*)t.ttref, (void*)t.tthslot, (void*)t.need_eval, (void*)t.eval_slot, (void*)t.eval_games,
+                    (void*)t.leafrec, (void*)t.goleaf})
+        s->pool.release(p);
+    if (net || cb) for (void* p : {(void*)s->d_batch, (void*)s->d_logits, (void*)s->d_value}) s->pool.release(p);
+    if (net) s->pool.release(s->d_id);
+    s->pool.adopt(fresh);
+    t.path = path; t.pact = pact; t.pstat = pstat; t.plen = plen; t.lstatus = lstatus; t.lvalue = lvalue; t.lhash = lhash;
+    t.ttstore = ttstore; t.ttref = ttref; t.tthslot = tthslot; t.need_eval = need_eval; t.eval_slot = eval_slot;
+    t.eval_games = eval_games; t.leafrec = leafrec; t.goleaf = goleaf;
+    if (net || cb) { s->d_batch = batch; s->d_logits = logits; s->d_value = value; t.net_logits = logits; t.net_value = value; }
+    if (net) s->d_id = id;
+    s->leaves = K;
+    return 0;
+}
+
+int az_search_leaves(az_search* s, int* leaves) {
+    if (!s || !leaves) return az_fail(AZ_ERR_ARG, "null argument");
+    std::lock_guard<std::mutex> lk(s->mu);
+    *leaves = s->leaves;
+    return 0;
 }
 
 int az_search_options(az_search* s, az_search_opts* out) {
@@ -1127,6 +1252,8 @@ int az_search_set_gomoku_rules(az_search* s, const az_gomoku_rules* r) {
     if (r->pro_long_opening) return az_fail(AZ_ERR_ARG, "the pro-long opening is not supported");
     if (s->used) return az_fail(AZ_ERR_STATE, "az_search_set_gomoku_rules: the handle has searched or moved; the rules are set before");
     const int renju = r->renju != 0, omok = r->omok != 0;
+    if ((renju || omok) && s->leaves > 1)
+        return az_fail(AZ_ERR_ARG, "Renju / Omok on a handle with leaves = %d (set leaves = 1 first)", s->leaves);
     if ((renju || omok) && !s->t.gforb) {
         uint64_t* m = nullptr;
         if (int e = s->pool.alloc(&m, (size_t)s->c.n_games * AZ_FORB_WORDS)) return e;

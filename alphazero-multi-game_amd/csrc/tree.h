@@ -66,6 +66,10 @@ struct TreeDev {
     int* gresult;                // [G] GameResult of the root state
     uint64_t* gforb;             // [G][AZ_FORB_WORDS] Renju / Omok: forbidden-cell mask of the selected leaf (Black to
                                  // move), from the selection to the expansion; null without rules
+    // Per-step scratch, from `gforb` above to `goleaf` below (bar rhdr and n_eval): one row per LEAF SLOT.  A
+    // handle with leaf parallelism K (az_search_set_leaves, search_host.h) holds G * K rows, slot q = g * K + j
+    // for descent j of game g's wave; at K = 1 -- and in the root steps of any handle -- the slot is the game,
+    // which is how the [G] below read
     int* path; int* plen;        // [G][AZ_DMAX], [G]
     int* pact;                   // [G][AZ_DMAX] action of every path node (pact[0] unused)
     int* lstatus; float* lvalue; uint64_t* lhash; int* ttstore; uint64_t* ttref; int* tthslot;

@@ -13,7 +13,12 @@ void az_launch_select(const TreeDev* t, int NA, int G, int mode, bool opt, bool 
 void az_launch_expand_select(const TreeDev* ts, const int* eval_slot, int eval_identity, int NA, int G, bool opt, bool rules,
                              hipStream_t st);
 void az_launch_expand_backup(const TreeDev* t, int G, int mode, bool opt, bool rules, hipStream_t st);
+// leaf parallelism (TreeDev scratch indexed by leaf slot g * K + j): one wave of k <= K descents per game, then its
+// k completions in descent order; k_scan_leaves compacts the n = G * K leaf slots
+void az_launch_wave_select(const TreeDev* t, int NA, int G, int K, int k, hipStream_t st);
+void az_launch_wave_expand(const TreeDev* t, int G, int K, int k, hipStream_t st);
 __global__ void k_scan(const TreeDev* __restrict__ tp);
+__global__ void k_scan_leaves(const TreeDev* __restrict__ tp, int n);
 __global__ void k_scan_nets(const TreeDev* __restrict__ tp, const uint8_t* __restrict__ slot_net, int n_nets);
 __global__ void k_select_action(const TreeDev* __restrict__ tp, int training, float temperature, const float* temps, int* actions, float* values, float* probs,
                                 int* child_actions, int* nchild);

@@ -591,10 +591,11 @@ __device__ void go_store_leaf(const TreeDev& t, int g, int lane, const uint8_t* 
     }
 }
 // go_build_leaf's results from the stored leaf state (same values: the replay is deterministic)
-__device__ void go_load_leaf(const TreeDev& t, int g, int lane, const int* sact, int depth, uint8_t* board, GoLds& L,
+// q: the leaf slot the state was stored under (the game itself without leaf parallelism)
+__device__ void go_load_leaf(const TreeDev& t, int g, int q, int lane, const int* sact, int depth, uint8_t* board, GoLds& L,
                              int* hist6, int& player, int& ko, int& passes, uint64_t& bh, uint64_t& hash) {
     const int A = t.A;
-    const uint8_t* src = t.goleaf + (size_t)g * AZ_GOLEAF_BYTES;
+    const uint8_t* src = t.goleaf + (size_t)q * AZ_GOLEAF_BYTES;
     const int* meta = reinterpret_cast<const int*>(src + 384);
     player = meta[0]; ko = meta[1]; passes = meta[2];
     const int nph = meta[3];
@@ -730,9 +731,16 @@ struct ExpLds {
 // default instantiation (OPT = false) is the plain PUCT search and reads none of them.
 // RULES: Renju / Omok (TreeDev renju / omok) are in force: a Black-to-move leaf gets its forbidden-cell
 // mask (t.gforb, which the expansion reads) and is a DRAW when no legal cell is left (is_stalemate).
-template <int IT, bool OPT, bool RULES>
-__device__ __forceinline__ void select_game(const TreeDev& t, int mode, const RootHint* hint, SelLds& SL, GoLds& gl) {
+// WAVE: descent wj of a wave of leaf-parallel descents (k_wave_select, handle setting leaves = wK > 1): its
+// scratch is leaf slot q = g * wK + wj.  The descent leaves its virtual loss on the tree for its wave-mates and
+// only classifies the leaf for the batch (terminal / needs the network): the TT probe reads the entry without
+// counting a lookup or a visit -- the completion (expand_game's WAVE instantiation) probes again, in descent
+// order, against the table and the leaf as its mates' completions left them.
+template <int IT, bool OPT, bool RULES, bool WAVE = false>
+__device__ __forceinline__ void select_game(const TreeDev& t, int mode, const RootHint* hint, SelLds& SL, GoLds& gl,
+                                            int wj = 0, int wK = 1) {
     const int g = blockIdx.x;
+    const int q = WAVE ? g * wK + wj : g;             // leaf slot: the index of the per-step scratch
     const int lane = threadIdx.x;
     auto& board = SL.board;
     auto& spath = SL.spath;
@@ -757,7 +765,7 @@ __device__ __forceinline__ void select_game(const TreeDev& t, int mode, const Ro
     const long long c_look = cnt[CNT_LOOKUPS], c_hits = cnt[CNT_HITS], c_bytes = cnt[CNT_BYTES_SEL];
     tstamp(t, g, 0, 0);
     if (!active) {
-        if (lane == 0) { t.lstatus[g] = ST_NONE; t.need_eval[g] = 0; }
+        if (lane == 0) { t.lstatus[q] = ST_NONE; t.need_eval[q] = 0; }
         return;
     }
     const size_t base = (size_t)g * t.ncap;
@@ -776,7 +784,7 @@ __device__ __forceinline__ void select_game(const TreeDev& t, int mode, const Ro
     if (mode != MODE_SIM) {
         // Root expansion: expandNode (noise) / search() root branch.
         if ((nflag & (FL_EXPANDED | FL_TERMINAL)) || gres != R_ONGOING) {
-            if (lane == 0) { t.lstatus[g] = ST_NONE; t.need_eval[g] = 0; }
+            if (lane == 0) { t.lstatus[q] = ST_NONE; t.need_eval[q] = 0; }
             return;
         }
         if (lane == 0) spath[0] = root;
@@ -876,11 +884,13 @@ __device__ __forceinline__ void select_game(const TreeDev& t, int mode, const Ro
         // addVirtualLoss on every path node, root a second time (parallel_mcts.cpp:293-295), on the
         // statistics the descent loaded (the wave is the tree's only writer); the post-VL values also
         // go to the path record (pstat), which the expansion's backup reads instead of the nodes
+        // (WAVE: no path record -- the nodes change under the wave-mates' descents and completions, so
+        // the completion reads them again)
         int4* ps = t.pstat + (size_t)g * AZ_DMAX;
         if (lane == 0) {
             rN += t.vl; rVL += t.vl; rW = rW - (float)t.vl;
             nd.N[root] = rN; nd.VL[root] = rVL; nd.W[root] = rW;
-            ps[0] = int4{rN, rVL, __float_as_int(rW), depth == 0 ? (int)nflag : 0};
+            if (!WAVE) ps[0] = int4{rN, rVL, __float_as_int(rW), depth == 0 ? (int)nflag : 0};
         }
         __syncthreads();
         for (int i = 1 + lane; i <= depth; i += 64) {
@@ -888,7 +898,7 @@ __device__ __forceinline__ void select_game(const TreeDev& t, int mode, const Ro
             const int N = sN[i] + t.vl, VL = sVL[i] + t.vl;
             const float W = sW[i] - (float)t.vl;
             nd.N[n] = N; nd.VL[n] = VL; nd.W[n] = W;
-            ps[i] = int4{N, VL, __float_as_int(W), i == depth ? (int)nflag : 0};   // .w: the leaf's flag
+            if (!WAVE) ps[i] = int4{N, VL, __float_as_int(W), i == depth ? (int)nflag : 0};   // .w: the leaf's flag
         }
     }
     __syncthreads();
@@ -900,7 +910,7 @@ __device__ __forceinline__ void select_game(const TreeDev& t, int mode, const Ro
     uint64_t gbh = 0;
     if (go) {
         go_build_leaf(t, g, lane, sact, depth, board, gl, hist6, player, gko, gpass, gbh, hash);
-        go_store_leaf(t, g, lane, board, gl, player, gko, gpass, gbh);
+        go_store_leaf(t, q, lane, board, gl, player, gko, gpass, gbh);
     } else {
         // leaf board = root board + path moves (distinct cells, lane-parallel); hash = root hash ^
         // the path's piece keys ^ the side-to-move keys (build_leaf, on registers already loaded)
@@ -916,12 +926,13 @@ __device__ __forceinline__ void select_game(const TreeDev& t, int mode, const Ro
     }
     int nlegal = 1;              // RULES: legal cells of a Black-to-move leaf that is not known to be over
     if (RULES && !go && player == 1 && !(nflag & FL_TERMINAL))
-        nlegal = forbidden_mask_wave(t, board, lane, t.gforb + (size_t)g * AZ_FORB_WORDS);
+        nlegal = forbidden_mask_wave(t, board, lane, t.gforb + (size_t)q * AZ_FORB_WORDS);
     tstamp(t, g, 0, 3);
     const int leaf = node;
     int store = 0;
     uint64_t ref = 0;
     int hslot = 0;
+    bool wskip = false;                 // WAVE: the leaf cannot need the evaluator (no batch row)
     long long d_look = 0, d_hits = 0;   // counter increments (written once at the end)
 
     if (mode == MODE_SIM) {
@@ -960,7 +971,9 @@ __device__ __forceinline__ void select_game(const TreeDev& t, int mode, const Ro
                 const int vis = t.tt_visits[tb + hs];
                 const uint64_t th = t.tt_hash[tb + hs];
                 const float tv = t.tt_value[tb + hs];
-                if (vis > 0 && th == hash) {
+                if (WAVE) {
+                    status = ST_EXPANDED;              // never evaluated; the completion makes the lookup
+                } else if (vis > 0 && th == hash) {
                     status = ST_EXPVAL;
                     value = tv;
                     if (lane == 0) t.tt_visits[tb + hs] = vis + 1;
@@ -976,7 +989,7 @@ __device__ __forceinline__ void select_game(const TreeDev& t, int mode, const Ro
         // has the pass
         if (lane == 0) {
             nd.flag[leaf] = (uint8_t)(nflag | FL_TERMINAL | FL_EXPANDED | (R_DRAW << 2));   // no lookups: counters unchanged
-            t.lstatus[g] = ST_NONE; t.need_eval[g] = 0;
+            t.lstatus[q] = ST_NONE; t.need_eval[q] = 0;
         }
         return;
     }
@@ -991,7 +1004,21 @@ __device__ __forceinline__ void select_game(const TreeDev& t, int mode, const Ro
         const float tv = t.tt_value[tb + hslot];
         const uint64_t tr = t.tt_ref[tb + hslot];
         const bool hit = vis > 0 && th == hash;
-        if (hit) {
+        if (WAVE) {
+            // An unexpanded, ongoing leaf: the completion decides between a TT hit, a wave-mate's expansion
+            // and an evaluation.  It can need the evaluator unless the entry is a hit no wave-mate's store
+            // can replace (visits >= 5 never drop): every other leaf gets its record and a batch row
+            status = ST_EVAL;
+            wskip = hit && vis >= 5;
+            if (!wskip) {
+                if (go) {
+                    go_groups(t, board, gl, lane, 64);
+                    go_write_leafrec(t, q, lane, board, gl, player, gko);
+                } else {
+                    write_leafrec(t, q, lane, board, hist6, player);
+                }
+            }
+        } else if (hit) {
             status = ST_TTHIT;
             value = tv;
             ref = tr;
@@ -1004,29 +1031,29 @@ __device__ __forceinline__ void select_game(const TreeDev& t, int mode, const Ro
             tstamp(t, g, 0, 5);
             if (go) {
                 go_groups(t, board, gl, lane, 64);
-                go_write_leafrec(t, g, lane, board, gl, player, gko);
+                go_write_leafrec(t, q, lane, board, gl, player, gko);
             } else {
-                write_leafrec(t, g, lane, board, hist6, player);
+                write_leafrec(t, q, lane, board, hist6, player);
             }
         }
     }
     if (lane == 0) {
-        t.lstatus[g] = status;
-        t.lvalue[g] = value;
-        t.lhash[g] = hash;
-        t.ttstore[g] = store;
-        t.ttref[g] = ref;
-        t.tthslot[g] = hslot;
-        t.plen[g] = depth + 1;
-        t.need_eval[g] = (status == ST_EVAL && (t.eval_kind == 0 || t.eval_kind == 4)) ? 1 : 0;
-        if (mode == MODE_SIM) t.rhdr[g] = rhdr0;        // the root-header record (the next expansion's hint)
+        t.lstatus[q] = status;
+        t.lvalue[q] = value;
+        t.lhash[q] = hash;
+        t.ttstore[q] = store;
+        t.ttref[q] = ref;
+        t.tthslot[q] = hslot;
+        t.plen[q] = depth + 1;
+        t.need_eval[q] = (status == ST_EVAL && !wskip && (t.eval_kind == 0 || t.eval_kind == 4)) ? 1 : 0;
+        if (!WAVE && mode == MODE_SIM) t.rhdr[g] = rhdr0;        // the root-header record (the next expansion's hint)
     }
     for (int i = lane; i <= depth; i += 64) {
-        t.path[(size_t)g * AZ_DMAX + i] = spath[i];
-        t.pact[(size_t)g * AZ_DMAX + i] = i ? sact[i] : -1;
+        t.path[(size_t)q * AZ_DMAX + i] = spath[i];
+        t.pact[(size_t)q * AZ_DMAX + i] = i ? sact[i] : -1;
     }
     tstamp(t, g, 0, 6);
-    if (lane == 0) { cnt[CNT_LOOKUPS] = c_look + d_look; cnt[CNT_HITS] = c_hits + d_hits; }
+    if (!WAVE && lane == 0) { cnt[CNT_LOOKUPS] = c_look + d_look; cnt[CNT_HITS] = c_hits + d_hits; }
     if (lane == 0 && mode == MODE_SIM) {
         // algorithmic bytes: child scans (whole 25 B records: N, W, VL, P + the child's header),
         // root header (21 B), VL read-modify-write (12 B + 12 B) and piece key (8 B) per path
@@ -1079,14 +1106,14 @@ __global__ void k_leaf_moves(TreeDev t, int* moves, int* len) {
 }
 
 // K2: deterministic compaction of the leaves that need the network (one block).
-__global__ __launch_bounds__(1024) void k_scan(const TreeDev* __restrict__ tp) {
-    const TreeDev& t = *tp;
+// n: the records scanned -- the games, or with leaf parallelism the G * K leaf slots (k_scan_leaves)
+__device__ __forceinline__ void scan_leaves(const TreeDev& t, const int n) {
     __shared__ int part[1024];
     const int tid = threadIdx.x;
-    const int per = (t.G + 1023) / 1024;
+    const int per = (n + 1023) / 1024;
     const int b0 = tid * per;
     int s = 0;
-    for (int i = 0; i < per; ++i) { int g = b0 + i; if (g < t.G) s += t.need_eval[g]; }
+    for (int i = 0; i < per; ++i) { int g = b0 + i; if (g < n) s += t.need_eval[g]; }
     part[tid] = s;
     __syncthreads();
     for (int o = 1; o < 1024; o <<= 1) {
@@ -1098,12 +1125,20 @@ __global__ __launch_bounds__(1024) void k_scan(const TreeDev* __restrict__ tp) {
     int off = part[tid] - s;
     for (int i = 0; i < per; ++i) {
         int g = b0 + i;
-        if (g < t.G) {
+        if (g < n) {
             if (t.need_eval[g]) { t.eval_slot[g] = off; t.eval_games[off] = g; ++off; }
             else t.eval_slot[g] = -1;
         }
     }
     if (tid == 1023) *t.n_eval = part[1023];
+}
+__global__ __launch_bounds__(1024) void k_scan(const TreeDev* __restrict__ tp) {
+    const TreeDev& t = *tp;
+    scan_leaves(t, t.G);
+}
+__global__ __launch_bounds__(1024) void k_scan_leaves(const TreeDev* __restrict__ tp, int n) {
+    const TreeDev& t = *tp;
+    scan_leaves(t, n);
 }
 
 // K2 of a handle whose slots are evaluated by different nets (az_search_set_slot_nets): the stable
@@ -1163,9 +1198,17 @@ __global__ __launch_bounds__(1024) void k_scan_nets(const TreeDev* __restrict__ 
 // then the leaf's network outputs and the path nodes' statistics -- the second and last one.
 // The Gomoku leaf board is the root board plus the path moves (no Zobrist work: k_select stored
 // the leaf hash); a Go leaf's position comes back from the state k_select stored (go_load_leaf).
-template <bool OPT, bool RULES>
-__device__ __forceinline__ void expand_game(const TreeDev& t, int mode, ExpLds& EL, GoLds& gl, RootHint* hint = nullptr) {
+// WAVE: completion wj of a wave (k_wave_expand; leaf slot q = g * wK + wj), applied after completions 0 .. wj-1 of
+// the same game: what k_select's single descent could settle at selection time is settled here instead, on the
+// tree and the table as the wave-mates left them -- the leaf's flag and the TT entry are read again (a mate may
+// have expanded the leaf, stored its entry, or replaced the entry selection saw), the lookup / hit counters and
+// the entry's visit count move here, and the backup reads the path nodes' statistics from the nodes (every path
+// shares the root with its mates' backups), not from the path record.
+template <bool OPT, bool RULES, bool WAVE = false>
+__device__ __forceinline__ void expand_game(const TreeDev& t, int mode, ExpLds& EL, GoLds& gl, RootHint* hint = nullptr,
+                                            int wj = 0, int wK = 1) {
     const int g = blockIdx.x;
+    const int q = WAVE ? g * wK + wj : g;             // leaf slot: the index of the per-step scratch
     const int lane = threadIdx.x;
     if (hint && lane == 0) hint->valid = 0;
     constexpr int NPAD = EXP_NPAD;
@@ -1182,12 +1225,12 @@ __device__ __forceinline__ void expand_game(const TreeDev& t, int mode, ExpLds& 
     if (g >= t.G) return;
     const int A = t.A, NA = t.NA;
     // ---- round trip 1
-    const size_t pb = (size_t)g * AZ_DMAX;
-    const int status = t.lstatus[g];
-    const int plen = t.plen[g];
-    const float lvalue = t.lvalue[g];
-    const uint64_t lhash = t.lhash[g];
-    const int slot = t.eval_identity ? g : t.eval_slot[g];
+    const size_t pb = (size_t)q * AZ_DMAX;
+    int status = t.lstatus[q];
+    const int plen = t.plen[q];
+    const float lvalue = t.lvalue[q];
+    const uint64_t lhash = t.lhash[q];
+    const int slot = t.eval_identity ? q : t.eval_slot[q];
     const int pth0 = t.path[pb + lane], pac0 = t.pact[pb + lane];
     const int pth1 = lane < AZ_DMAX - 64 ? t.path[pb + 64 + lane] : 0;
     const int pac1 = lane < AZ_DMAX - 64 ? t.pact[pb + 64 + lane] : -1;
@@ -1195,27 +1238,29 @@ __device__ __forceinline__ void expand_game(const TreeDev& t, int mode, ExpLds& 
     // unused) and, with an identity batch, the leaf's network outputs: no second round trip
     const bool sim = mode == MODE_SIM;
     int4 ps0 = int4{0, 0, 0, 0}, ps1 = int4{0, 0, 0, 0};
-    if (sim) {
+    if (sim && !WAVE) {
         ps0 = t.pstat[pb + lane];
         if (lane < AZ_DMAX - 64) ps1 = t.pstat[pb + 64 + lane];
     }
-    const int4 rh = sim ? t.rhdr[g] : int4{0, 0, 0, 0};   // the root's header as k_select left it
+    const int4 rh = sim && !WAVE ? t.rhdr[g] : int4{0, 0, 0, 0};   // the root's header as k_select left it
     int rfirst = rh.x, rcnt = rh.y, rflag = rh.z;
     const bool lg_early = t.eval_identity && (t.eval_kind == 0 || t.eval_kind == 4);
     float lg[PK];
     float netv = 0.0f;
     if (lg_early) {
-        const float* src = t.net_logits + (size_t)g * NA;
+        const float* src = t.net_logits + (size_t)q * NA;
 #pragma unroll
         for (int k = 0; k < PK; ++k) lg[k] = lane + 64 * k < NA ? src[lane + 64 * k] : 0.0f;
-        netv = t.net_value[g];
+        netv = t.net_value[q];
     }
     uint8_t rb[BK];
 #pragma unroll
     for (int k = 0; k < BK; ++k) rb[k] = lane + 64 * k < A ? t.rboard[(size_t)g * A + lane + 64 * k] : 0;
     const int p0 = t.rplayer[g], rstones = t.rstones[g], rfresh = t.rfresh[g];
-    const int atop = t.atop[g], ttstore = t.ttstore[g], tthslot = t.tthslot[g];
-    const uint64_t ring_cur = t.ring_cur[g], ttref = t.ttref[g];
+    const int atop = t.atop[g];
+    int ttstore = t.ttstore[q], tthslot = t.tthslot[q];
+    const uint64_t ring_cur = t.ring_cur[g];
+    uint64_t ttref = t.ttref[q];
     long long* cnt = t.cnt + (size_t)g * AZ_NCNT;
     const long long c_ev = cnt[CNT_EVALS], c_evt = cnt[CNT_EVALS_TOTAL], c_sims = cnt[CNT_SIMS], c_bytes = cnt[CNT_BYTES_EXP];
     tstamp(t, g, 1, 0);
@@ -1231,15 +1276,22 @@ __device__ __forceinline__ void expand_game(const TreeDev& t, int mode, ExpLds& 
     GamePtrs nd = game_nodes(t.nd, base);
     const int depth = plen - 1;
     // ---- round trip 2 (batches that are not the identity): the leaf's network outputs
-    const bool net_in = status == ST_EVAL && (t.eval_kind == 0 || t.eval_kind == 4);
+    // (WAVE: a leaf selection gave no batch row has slot -1 and loads nothing)
+    const bool net_in = status == ST_EVAL && (t.eval_kind == 0 || t.eval_kind == 4) && (!WAVE || slot >= 0);
     if (net_in && !lg_early) {
         const float* src = t.net_logits + (size_t)slot * NA;
 #pragma unroll
         for (int k = 0; k < PK; ++k) lg[k] = lane + 64 * k < NA ? src[lane + 64 * k] : 0.0f;
         netv = t.net_value[slot];
     }
-    const int bN0 = ps0.x, bVL0 = ps0.y, bN1 = ps1.x, bVL1 = ps1.y;
-    const float bW0 = __int_as_float(ps0.z), bW1 = __int_as_float(ps1.z);
+    int bN0 = ps0.x, bVL0 = ps0.y, bN1 = ps1.x, bVL1 = ps1.y;
+    float bW0 = __int_as_float(ps0.z), bW1 = __int_as_float(ps1.z);
+    if (WAVE && sim) {
+        // the path nodes as the earlier descents and completions of this wave left them (entries past the
+        // path are stale: not loaded)
+        if (lane <= depth) { bN0 = nd.N[pth0]; bVL0 = nd.VL[pth0]; bW0 = nd.W[pth0]; }
+        if (lane + 64 <= depth) { bN1 = nd.N[pth1]; bVL1 = nd.VL[pth1]; bW1 = nd.W[pth1]; }
+    }
 
     spath[lane] = pth0; sact[lane] = pac0;
     if (lane < AZ_DMAX - 64) { spath[64 + lane] = pth1; sact[64 + lane] = pac1; }
@@ -1248,7 +1300,7 @@ __device__ __forceinline__ void expand_game(const TreeDev& t, int mode, ExpLds& 
     uint64_t gbh = 0;
     if (go) {
         __syncthreads();
-        go_load_leaf(t, g, lane, sact, depth, board, gl, hist6, player, gko, gpass, gbh, hash);
+        go_load_leaf(t, g, q, lane, sact, depth, board, gl, hist6, player, gko, gpass, gbh, hash);
     } else {
 #pragma unroll
         for (int k = 0; k < BK; ++k) if (lane + 64 * k < A) board[lane + 64 * k] = rb[k];
@@ -1264,6 +1316,38 @@ __device__ __forceinline__ void expand_game(const TreeDev& t, int mode, ExpLds& 
     const int leaf = spath[depth];
     float value = lvalue;
     long long ev_add = 0;
+    int wflag = 0;                                   // WAVE: the leaf's flag as completion wj finds it
+    long long w_look = 0, w_hits = 0;
+    if (WAVE && status != ST_TERMINAL) {
+        // runSingleSimulation from its TT lookup on (parallel_mcts.cpp:319-346), now: a hit expands the leaf
+        // unless a wave-mate did ("another thread expanded it"); a miss on an expanded leaf takes getValue();
+        // otherwise evaluateState (its own lookup), store, expand
+        wflag = nd.flag[leaf];
+        const size_t tb = (size_t)g * t.tt_slots;
+        tthslot = (int)(lhash & t.tt_mask);
+        const int vis = t.tt_visits[tb + tthslot];
+        const uint64_t th = t.tt_hash[tb + tthslot];
+        const float tv = t.tt_value[tb + tthslot];
+        const uint64_t tr = t.tt_ref[tb + tthslot];
+        if (vis > 0 && th == lhash) {
+            status = (wflag & FL_EXPANDED) ? ST_EXPVAL : ST_TTHIT;
+            value = tv;
+            ttref = tr;
+            if (lane == 0) t.tt_visits[tb + tthslot] = vis + 1;
+            w_look = 1; w_hits = 1;
+        } else if (wflag & FL_EXPANDED) {
+            status = ST_EXPANDED;
+            w_look = 1;
+        } else {
+            status = ST_EVAL;
+            ttstore = vis < 5 ? 1 : 0;               // empty slot, or shouldReplace (visits < 5)
+            w_look = 2;
+            if ((t.eval_kind == 0 || t.eval_kind == 4) && slot < 0) {   // no batch row: selection's rule is wrong
+                if (lane == 0) atomicOr(t.err, ERR_BATCH);
+                return;
+            }
+        }
+    }
     // algorithmic bytes: path (4 + 4 B per level), root board, then below: policy / TT / ring,
     // new child records (25 B), VL-removal + backup read-modify-write (24 B per path node)
     long long kb = (long long)plen * 8 + A;
@@ -1282,7 +1366,7 @@ __device__ __forceinline__ void expand_game(const TreeDev& t, int mode, ExpLds& 
             n = A - rstones;   // fresh root is the empty board
         } else {
             // RULES: a Black-to-move leaf's legal cells leave out the mask k_select built for it
-            const uint64_t* forb = RULES && player == 1 ? t.gforb + (size_t)g * AZ_FORB_WORDS : nullptr;
+            const uint64_t* forb = RULES && player == 1 ? t.gforb + (size_t)q * AZ_FORB_WORDS : nullptr;
             for (int c0 = 0; c0 < A; c0 += 64) {
                 const int a = A - 1 - (c0 + lane);
                 bool e = a >= 0 && board[a] == 0;
@@ -1374,7 +1458,7 @@ __device__ __forceinline__ void expand_game(const TreeDev& t, int mode, ExpLds& 
                     for (int a = lane; a < NA; a += 64) t.log_pol[(size_t)k * NA + a] = pol[a];
                     if (t.log_planes) {
                         const int npl = go ? 8 : 11;
-                        const uint8_t* rec = t.leafrec + (size_t)g * AZ_REC_BYTES;
+                        const uint8_t* rec = t.leafrec + (size_t)q * AZ_REC_BYTES;
                         for (int a = lane; a < A; a += 64) {
                             float c[16];
                             az_leaf_planes(rec, go, t.bs, a, c);
@@ -1442,7 +1526,7 @@ __device__ __forceinline__ void expand_game(const TreeDev& t, int mode, ExpLds& 
             }
         }
         // the leaf's flag: k_select left it in the path record (a simulation step), else from the node
-        const int lfw = lane_bcast(depth < 64 ? ps0.w : ps1.w, depth & 63);
+        const int lfw = WAVE ? wflag : lane_bcast(depth < 64 ? ps0.w : ps1.w, depth & 63);
         if (lane == 0) {
             t.atop[g] = first + n;
             const uint8_t fl = (uint8_t)((sim ? (uint8_t)lfw : nd.flag[leaf]) | FL_EXPANDED);
@@ -1507,6 +1591,7 @@ __device__ __forceinline__ void expand_game(const TreeDev& t, int mode, ExpLds& 
     if (lane == 0) {
         if (ev_add) { cnt[CNT_EVALS] = c_ev + 1; cnt[CNT_EVALS_TOTAL] = c_evt + 1; }
         if (sim) { cnt[CNT_SIMS] = c_sims + 1; cnt[CNT_BYTES_EXP] = c_bytes + kb; }
+        if (WAVE) { cnt[CNT_LOOKUPS] += w_look; cnt[CNT_HITS] += w_hits; }
     }
     tstamp(t, g, 1, 7);
 }
@@ -1561,6 +1646,44 @@ void az_launch_expand_select(const TreeDev* ts, const int* eval_slot, int eval_i
         else launch_expand_select<false, true>(ts, eval_slot, eval_identity, NA, G, st);
     } else if (opt) launch_expand_select<true, false>(ts, eval_slot, eval_identity, NA, G, st);
     else launch_expand_select<false, false>(ts, eval_slot, eval_identity, NA, G, st);
+}
+
+// Leaf parallelism (handle setting leaves = K > 1, az_search_set_leaves): a simulation step is a wave of k <= K
+// descents per game, all made before any of their leaves is completed -- ParallelMCTS with numThreads = k in the
+// interleaving where every worker has put its virtual loss on its path (parallel_mcts.cpp:295) before any of them
+// looks at its leaf (:297), the workers then finishing in order.  The game's one wavefront loops the shared
+// selection / expansion over the k leaf slots q = g * K + j; between two iterations a block barrier (with its
+// work-group release / acquire) makes the wave's own stores to the tree, the table and the cursors visible to its
+// next loads, as between the two halves of k_expand_select.  K = 1 handles never launch these kernels.
+template <int IT>
+__global__ __launch_bounds__(64) void k_wave_select(const TreeDev* __restrict__ tp, int K, int k) {
+    const TreeDev& t = *tp;
+    __shared__ SelLds SL;
+    __shared__ GoLds gl;
+    for (int j = 0; j < k; ++j) {
+        select_game<IT, false, false, true>(t, MODE_SIM, nullptr, SL, gl, j, K);
+        __syncthreads();
+    }
+    // a short wave (the last of a search whose simulations K does not divide): the other slots hold no leaf
+    const int g = blockIdx.x, j = k + (int)threadIdx.x;
+    if (g < t.G && j < K) { t.lstatus[g * K + j] = ST_NONE; t.need_eval[g * K + j] = 0; }
+}
+__global__ __launch_bounds__(64) void k_wave_expand(const TreeDev* __restrict__ tp, int K, int k) {
+    const TreeDev& t = *tp;
+    __shared__ ExpLds EL;
+    __shared__ GoLds gl;
+    for (int j = 0; j < k; ++j) {
+        expand_game<false, false, true>(t, MODE_SIM, EL, gl, nullptr, j, K);
+        __syncthreads();
+    }
+}
+void az_launch_wave_select(const TreeDev* t, int NA, int G, int K, int k, hipStream_t st) {
+    if (NA <= 128) hipLaunchKernelGGL((k_wave_select<2>), dim3(G), dim3(64), 0, st, t, K, k);
+    else if (NA <= 256) hipLaunchKernelGGL((k_wave_select<4>), dim3(G), dim3(64), 0, st, t, K, k);
+    else hipLaunchKernelGGL((k_wave_select<(AZ_MAXNA + 63) / 64>), dim3(G), dim3(64), 0, st, t, K, k);
+}
+void az_launch_wave_expand(const TreeDev* t, int G, int K, int k, hipStream_t st) {
+    hipLaunchKernelGGL(k_wave_expand, dim3(G), dim3(64), 0, st, t, K, k);
 }
 
 // K4: visit distribution, action choice and root value per game.

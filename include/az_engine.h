@@ -352,6 +352,25 @@ int az_search_set_net(az_search* s, az_net* net);
  * a single-net handle with its own net.  A later az_search_set_net returns to one net. */
 #define AZ_MAX_SLOT_NETS 4
 int az_search_set_slot_nets(az_search* s, az_net* const* nets, int n_nets, const uint8_t* slot_net);
+/* Leaf parallelism: with leaves = K > 1 a simulation step of a game is a wave -- K descents from the root one
+ * after the other, each seeing the virtual loss of the ones before it; then every leaf of every game that needs
+ * the evaluator goes through it as ONE batch of up to n_games x K positions; then the K completions (TT store,
+ * expansion, backup) in descent order.  This is ParallelMCTS with MCTSConfig::numThreads = K in the interleaving
+ * where every worker has applied its virtual loss (parallel_mcts.cpp:295) before any looks at its leaf (:297) and
+ * the workers finish in order; two descents of a wave may end on one leaf (the later one takes the TT hit on its
+ * mate's store, or getValue() of the freshly expanded node where the table refused the store).  A search of
+ * num_simulations runs ceil(sims / K) waves, the last one short; az_search_simulate(n) likewise.  The net may
+ * run on more leaves than the completions consume: such forwards are dropped and are not counted in `evals`
+ * (nor logged by az_search_enable_eval_log).  K = 1 (the default) is the search one descent at a time.
+ * Set between searches; trees, tables, counters and generators are kept, the per-step scratch is reallocated
+ * from the handle's pool.  AZ_ERR_ARG (the handle unchanged) for K outside 1..AZ_MAX_LEAVES, for an AZ_EVAL_NET
+ * handle whose net has max_batch < n_games x K, and for K > 1 together with non-default az_search_opts, Renju /
+ * Omok, per-slot nets or AZ_EVAL_CALLBACK; on a handle with K > 1, az_search_set_options (non-default options),
+ * az_search_set_gomoku_rules (Renju / Omok) and az_search_set_slot_nets fail the same way, and az_search_set_net
+ * asks max_batch >= n_games x K. */
+#define AZ_MAX_LEAVES 32
+int az_search_set_leaves(az_search* s, int leaves);
+int az_search_leaves(az_search* s, int* leaves);
 /* Empty every game's transposition table, trees kept (ParallelMCTS::setTranspositionTable with a
  * new table, parallel_mcts.cpp:1209-1222). */
 int az_search_clear_tt(az_search* s);
