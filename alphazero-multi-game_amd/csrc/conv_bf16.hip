@@ -191,12 +191,6 @@ __global__ void k_split_bf16(const float* in, uint16_t* hi, uint16_t* lo, size_t
     }
 }
 
-void az_conv_bf16_launch(const ConvBf16Args& a, bool split, hipStream_t st) {
-    const int nbm = (a.M + 127) / 128, nbn = (a.N + 127) / 128;
-    if (split) hipLaunchKernelGGL(conv3x3_bf16<true>, dim3(nbm * nbn), dim3(256), 0, st, a);
-    else hipLaunchKernelGGL(conv3x3_bf16<false>, dim3(nbm * nbn), dim3(256), 0, st, a);
-}
-
 void az_launch_split_bf16(const float* in, uint16_t* hi, uint16_t* lo, size_t n, const int* m_limit, int rows_per_sample,
                           int C, hipStream_t st) {
     hipLaunchKernelGGL(k_split_bf16, dim3(2048), dim3(256), 0, st, in, hi, lo, n, m_limit, rows_per_sample, C);
@@ -1787,125 +1781,10 @@ int az_launch_pool_heads_g8(const uint16_t* hi, const int8_t* q, const float* Wt
     return hipGetLastError() == hipSuccess ? 0 : -2;
 }
 
-static int g_conv_flags = 4 | 0x200;   // bit 2: v6 (16x16x32) at 15x15; 0x200: v7 on 15x15 boards only
-// Variant bits for A/B measurement inside one process (tools/net_bench.py --flags): 0x2000 selects
-// conv3x3_v7's per-tap main loop on the SLIM tile (g8_choice below), 0x4000 keeps the row-streamed
-// loop's unpeeled tile tail (the last chunk reloads itself, the residual join reads global memory);
-// no others defined now
-// (a residual L2 prefetch during the main loop measured 0.6% slower and was removed; a cross-row
-// fragment prefetch and a mid-row barrier variant measured 1.5-2% slower)
+static int g_conv_flags = CONV_F_DEFAULT;   // the variant bits: conv_plan.h's table
 extern "C" int az_diag_set_conv_flags(int flags) { g_conv_flags = flags; return 0; }
 extern "C" int az_diag_conv_flags(void) { return g_conv_flags; }   // the current set (bench.py ORs bits into it)
 int az_conv_flags() { return g_conv_flags; }
-
-template <int HB, bool DENSE>
-static void v6_launch_g(const ConvBf16Args& a, int mode, hipStream_t st) {
-    typedef G8Geom<HB, DENSE> GM;
-    const int boards = a.M / GM::HW;
-    const int groups = GM::FLAT ? (boards * GM::S + 511) / 512 : (boards + GM::BOARDS - 1) / GM::BOARDS;
-    const int grid = (groups + 7) / 8 * 8 * (a.N / 128);   // XCD-aware group/half mapping: whole groups of 8
-    if (mode == 2) hipLaunchKernelGGL((conv3x3_v6<2, HB, DENSE>), dim3(grid), dim3(512), 0, st, a);
-    else hipLaunchKernelGGL((conv3x3_v6<1, HB, DENSE>), dim3(grid), dim3(512), 0, st, a);
-}
-// DENSE is the default for every board but 15x15, where two padded boards fill a 512-row tile
-// at 88% and B = 2048 comes to exactly 8 rounds of 256 blocks (dense: 1800 blocks, still 8
-// rounds, plus the masking).  Measured at B = 2048 (tools/net_bench.py --flags 0x4,0xc): dense
-// 19x19 -3.1%, 13x13 -4.0%, 9x9 -14%, 8x8 (C5) -20% trunk time; 15x15 +8.7%.
-// Flag 8 forces DENSE, flag 0x4000000 the padded geometry (A/B measurement).
-template <int HB>
-static void v6_launch(const ConvBf16Args& a, int mode, hipStream_t st) {
-    const bool dense = (a.flags & 8) || (HB != 15 && !(a.flags & 0x4000000));
-    if (dense) v6_launch_g<HB, true>(a, mode, st);
-    else v6_launch_g<HB, false>(a, mode, st);
-}
-
-// Which kernel az_conv_g8_launch takes for a layer (a.flags already set): 0 none (unsupported),
-// 1 conv3x3_v7 (*geo = its 15x15 tile geometry), 2 conv3x3_v6 (*geo = 1 when DENSE), 3 conv3x3_v5.
-static int g8_choice(const ConvBf16Args& a, int* geo) {
-    if (a.H != a.W || !az_conv_g8_supported(a.H, a.W, a.C, a.N)) return 0;
-    // conv3x3_v7 (conv_v7.hip, two 256-thread blocks per CU, epilogue from registers) takes every
-    // layer it supports (trunk convs: C % 64 == 0) unless flag 0x100 selects v6 (A/B measurement);
-    // flag 0x200: v7 only on 15x15 boards; 15x15 tile geometry: SLIM (default), flag 8 DENSE, 0x400 PAD.
-    // 15x15 below 1024 boards: a launch is one or two rounds of blocks and v6 is faster (B = 256: 61
-    // vs 65 us); the other boards take v7's small DENSE tiles there (next branch).  Flag 0x800 forces
-    // v7 at any batch.  Flag 0x2000: the SLIM tile keeps conv3x3_v7's per-tap main loop (weight ring in
-    // LDS, one barrier per tap) instead of the row-streamed one (conv_v7.hip; A/B measurement, read by
-    // the kernel itself: a wave-uniform branch between the two compiled loops).
-    const int boards_g8 = a.M / (a.H * a.W);
-    if (!(a.flags & 0x100) && (a.H == 15 || !(a.flags & 0x200)) && (boards_g8 >= 1024 || (a.flags & 0x800)) &&
-        az_conv_v7_supported(a)) {
-        *geo = (a.flags & 8) ? 2 : (a.flags & 0x400) ? 0 : 1;
-        return 1;
-    }
-    // Small batches on the DENSE boards (the per-rank shards of the 8-GPU C4 / C5 configs): v6's
-    // 512-row tiles leave most CUs idle (C5 net, 128 boards: 32 blocks), conv3x3_v7 with 128 / 64-row
-    // tiles (az_conv_v7_tm) fills them -- 128 boards of 8x8: 0.0237 vs 0.0644 ms per launch; 19x19 on
-    // 128-row tiles with three blocks per CU: 0.0594 vs v6 0.0747 at 128 boards, 0.1106 vs 0.1375 at
-    // 256 (profiles/r04_small_batch_tiles_192.txt, r05_small_batch_ring3.txt).  Flag 0x1000 keeps v6.
-    if (!(a.flags & (0x100 | 0x1000)) && a.H != 15 && boards_g8 < 1024 && az_conv_v7_supported(a)) {
-        *geo = 2;
-        return 1;
-    }
-    if (a.a_tail < (size_t)a.M * a.C * 2) return 0;
-    // v6: the padding offset walks (C/32) chunk steps of 4*HW*16 B into the zeroed tail, and the
-    // buffer descriptor's 32-bit range must cover the activations plus that tail
-    const bool v6_ok = a.C % 32 == 0 && az_act_range_ok(a.a_tail) && az_tail_reach_ok(a.H, a.C);
-    if (a.H != 15 || ((a.flags & 4) && a.C % 32 == 0)) {
-        if (!v6_ok || !a.relu) return 0;                 // conv3x3_v6 always applies the ReLU
-        *geo = (a.flags & 8) || (a.H != 15 && !(a.flags & 0x4000000));
-        return 2;
-    }
-    return 3;
-}
-
-int az_conv_g8_launch(const ConvBf16Args& a_in, int mode, hipStream_t st) {
-    ConvBf16Args a = a_in;
-    a.flags = g_conv_flags;
-    if (a.a_tail == 0) a.a_tail = (size_t)a.M * a.C * 2;
-    int geo = 0;
-    switch (g8_choice(a, &geo)) {
-        case 1: return az_conv_v7_launch(a, mode, geo, st);
-        case 2:
-            switch (a.H) {
-                case 8: v6_launch<8>(a, mode, st); return 0;
-                case 9: v6_launch<9>(a, mode, st); return 0;
-                case 13: v6_launch<13>(a, mode, st); return 0;
-                case 19: v6_launch<19>(a, mode, st); return 0;
-                default: v6_launch<15>(a, mode, st); return 0;
-            }
-        case 3: break;
-        default: return -1;
-    }
-    const int boards = a.M / 225;
-    const int pairs = (boards + 1) / 2;
-    const int nsplit = a.N / 128;
-    const int grid = (pairs + 7) / 8 * 8 * nsplit;     // XCD-aware pair/half mapping needs whole groups of 8
-    if (mode == 2) hipLaunchKernelGGL((conv3x3_v5<2, 8>), dim3(grid), dim3(512), 0, st, a);
-    else hipLaunchKernelGGL((conv3x3_v5<1, 8>), dim3(grid), dim3(512), 0, st, a);
-    return 0;
-}
-
-// The name of the kernel az_conv_g8_launch takes for this layer (bench.py's roofline label)
-int az_conv_g8_name(const ConvBf16Args& a_in, int mode, char* out, int len) {
-    ConvBf16Args a = a_in;
-    a.flags = g_conv_flags;
-    if (a.a_tail == 0) a.a_tail = (size_t)a.M * a.C * 2;
-    int geo = 0;
-    static const char* g7[3] = {"PAD", "SLIM", "DENSE"};
-    switch (g8_choice(a, &geo)) {
-        case 1: {
-            const int g = a.H == 15 ? geo : 2, tm = g == 2 ? az_conv_v7_tm(a) : 256;
-            const int rg = tm != 256 ? az_conv_v7_ring(a) : 4;
-            if (rg != 4) snprintf(out, len, "conv3x3_v7<%d, %d, %s, %d, %d>", mode, a.H, g7[g], tm, rg);
-            else if (tm != 256) snprintf(out, len, "conv3x3_v7<%d, %d, %s, %d>", mode, a.H, g7[g], tm);
-            else snprintf(out, len, "conv3x3_v7<%d, %d, %s>", mode, a.H, g7[g]);
-            return 0;
-        }
-        case 2: snprintf(out, len, "conv3x3_v6<%d, %d%s>", mode, a.H, geo ? ", DENSE" : ""); return 0;
-        case 3: snprintf(out, len, "conv3x3_v5<%d, 8>", mode); return 0;
-        default: return -1;
-    }
-}
 
 // fp32 -> fp16 activations (first trunk input, AZ_PREC_FP16)
 __global__ void k_to_f16(const float* in, uint16_t* out, size_t n, const int* m_limit, int rows_per_sample, int C,
@@ -1925,60 +1804,91 @@ void az_launch_to_f16(const float* in, uint16_t* out, size_t n, const int* m_lim
     hipLaunchKernelGGL(k_to_f16, dim3(2048), dim3(256), 0, st, in, out, n, m_limit, rows_per_sample, C, ovf);
 }
 
-template <int BNT>
-static void v4_launch(const ConvBf16Args& a, int mode, int grid, hipStream_t st) {
-    // bf16x3 keeps the single-buffered schedule: the double buffer spills at 256 VGPRs
-    if (mode == 0) hipLaunchKernelGGL((conv3x3_v4<0, BNT, 0>), dim3(grid), dim3(512), 0, st, a);
-    else if (mode == 1) hipLaunchKernelGGL((conv3x3_v4<1, BNT, 1>), dim3(grid), dim3(512), 0, st, a);
-    else hipLaunchKernelGGL((conv3x3_v4<2, BNT, 1>), dim3(grid), dim3(512), 0, st, a);
-}
+// ---- executing a plan (conv_plan.h): each helper launches the one instantiation the plan's fields
+// name on the plan's grid
+#define CONV_LAUNCH(K) hipLaunchKernelGGL(K, dim3(p.grid), dim3(p.block), 0, st, a)
 
-void az_conv_v4_launch(const ConvBf16Args& a, int mode, hipStream_t st) {
-    const int boards = a.M / 225;
-    const int bnt = a.N % 128 == 0 ? 128 : 64;
-    if (mode == 0 && bnt == 64 && boards <= 512) {   // one board per block: fill the CUs at small batches
-        hipLaunchKernelGGL((conv3x3_v4<0, 64, 1, 1, 512>), dim3(boards * (a.N / 64)), dim3(512), 0, st, a);
-        return;
-    }
-    const int grid = (boards + 1) / 2 * (a.N / bnt);
-    if (bnt == 128) v4_launch<128>(a, mode, grid, st);
-    else v4_launch<64>(a, mode, grid, st);
-}
-
-// bf16 / bf16x3 trunk conv outside the g8 path: v4 on 15x15 boards, else v3 (N % 256 == 0 or
-// N == 64, C % 32 == 0), else v1 (128 x 128 register-staged tiles, any shape)
-static int bf16_choice(const ConvBf16Args& a) {
-    if (a.rows_per_sample == 225 && az_conv_v4_supported(a.H, a.W, a.C, a.N)) return 4;
-    if (a.C % 32 == 0 && (a.N % 256 == 0 || a.N == 64)) return 3;
-    return 1;
-}
-
-void az_conv_bf16_launch_v(const ConvBf16Args& a, bool split, hipStream_t st) {
-    switch (bf16_choice(a)) {
-        case 4: az_conv_v4_launch(a, split ? 0 : 1, st); return;
-        case 3:
-            if (a.N % 256 == 0) {
-                const int nbm = (a.M + 127) / 128, nbn = a.N / 256;
-                if (split) hipLaunchKernelGGL((conv3x3_v3<true, 128, 256, 2, 4>), dim3(nbm * nbn), dim3(512), 0, st, a);
-                else hipLaunchKernelGGL((conv3x3_v3<false, 128, 256, 2, 4>), dim3(nbm * nbn), dim3(512), 0, st, a);
-            } else {
-                const int nbm = (a.M + 255) / 256;
-                if (split) hipLaunchKernelGGL((conv3x3_v3<true, 256, 64, 4, 1>), dim3(nbm), dim3(256), 0, st, a);
-                else hipLaunchKernelGGL((conv3x3_v3<false, 256, 64, 4, 1>), dim3(nbm), dim3(256), 0, st, a);
-            }
-            return;
-        default: az_conv_bf16_launch(a, split, st); return;
-    }
-}
-
-// The name of the kernel az_conv_bf16_launch_v (mode 0 bf16x3 / 1 bf16) or, for fp16 (mode 2),
-// az_conv_v4_launch takes for this layer
-int az_conv_bf16_name(const ConvBf16Args& a, int mode, char* out, int len) {
-    const int c = mode == 2 ? 4 : bf16_choice(a);
-    const bool split = mode == 0;
-    if (c == 4) snprintf(out, len, "conv3x3_v4<%d, %d>", mode, a.N % 128 == 0 ? 128 : 64);
-    else if (c == 3) snprintf(out, len, a.N % 256 == 0 ? "conv3x3_v3<%s, 128, 256>" : "conv3x3_v3<%s, 256, 64>",
-                              split ? "split" : "bf16");
-    else snprintf(out, len, "conv3x3_bf16<%s>", split ? "split" : "bf16");
+template <int HB, bool DENSE>
+static int v6_launch_g(const ConvPlan& p, const ConvBf16Args& a, hipStream_t st) {
+    if (p.mode == 2) CONV_LAUNCH((conv3x3_v6<2, HB, DENSE>));
+    else CONV_LAUNCH((conv3x3_v6<1, HB, DENSE>));
     return 0;
+}
+
+// mode 0 (bf16 hi + lo) has the single-buffered schedule and the one-board variant of 64 channels,
+// modes 1 / 2 the double-buffered schedule
+static int v4_launch(const ConvPlan& p, const ConvBf16Args& a, hipStream_t st) {
+    const bool two = p.boards == 2 && p.nt == 512 && p.sched == (p.mode == 0 ? 0 : 1);
+    if (p.mode == 0 && p.bnt == 64 && p.sched == 1 && p.boards == 1 && p.nt == 512) CONV_LAUNCH((conv3x3_v4<0, 64, 1, 1, 512>));
+    else if (!two || (p.bnt != 128 && p.bnt != 64)) return -1;
+    else if (p.mode == 0 && p.bnt == 128) CONV_LAUNCH((conv3x3_v4<0, 128, 0>));
+    else if (p.mode == 0) CONV_LAUNCH((conv3x3_v4<0, 64, 0>));
+    else if (p.mode == 1 && p.bnt == 128) CONV_LAUNCH((conv3x3_v4<1, 128, 1>));
+    else if (p.mode == 1) CONV_LAUNCH((conv3x3_v4<1, 64, 1>));
+    else if (p.bnt == 128) CONV_LAUNCH((conv3x3_v4<2, 128, 1>));
+    else CONV_LAUNCH((conv3x3_v4<2, 64, 1>));
+    return 0;
+}
+
+int az_conv_launch(const ConvPlan& p, const ConvBf16Args& a, hipStream_t st) {
+    const bool g8_mode = p.mode == 1 || p.mode == 2, split = p.mode == 0;
+    switch (p.kernel) {
+        case CONV_V7: case CONV_V7X3: case CONV_V9X3: return az_conv_launch_v7(p, a, st);
+        case CONV_V6:
+            if (!g8_mode) return -1;
+            return az_conv_board_dispatch(p.board, [&](auto hb) -> int {
+                constexpr int HB = decltype(hb)::value;
+                if (p.geo == GEO_DENSE) return v6_launch_g<HB, true>(p, a, st);
+                if constexpr (HB == 15) if (p.geo == GEO_PAD) return v6_launch_g<15, false>(p, a, st);
+                return -1;
+            });
+        case CONV_V5:
+            if (!g8_mode || p.board != 15) return -1;
+            if (p.mode == 2) CONV_LAUNCH((conv3x3_v5<2, 8>));
+            else CONV_LAUNCH((conv3x3_v5<1, 8>));
+            return 0;
+        case CONV_V4: return p.mode >= 0 && p.mode <= 2 ? v4_launch(p, a, st) : -1;
+        case CONV_V3:
+            if (p.mode != 0 && p.mode != 1) return -1;
+            if (p.bm == 128 && p.bn == 256) {
+                if (split) CONV_LAUNCH((conv3x3_v3<true, 128, 256, 2, 4>));
+                else CONV_LAUNCH((conv3x3_v3<false, 128, 256, 2, 4>));
+            } else if (p.bm == 256 && p.bn == 64) {
+                if (split) CONV_LAUNCH((conv3x3_v3<true, 256, 64, 4, 1>));
+                else CONV_LAUNCH((conv3x3_v3<false, 256, 64, 4, 1>));
+            } else {
+                return -1;
+            }
+            return 0;
+        case CONV_BF16:
+            if (p.mode != 0 && p.mode != 1) return -1;
+            if (split) CONV_LAUNCH(conv3x3_bf16<true>);
+            else CONV_LAUNCH(conv3x3_bf16<false>);
+            return 0;
+        default: return -1;
+    }
+}
+#undef CONV_LAUNCH
+
+// ---- the three families: plan, then launch.  The flags reach the plans here and nowhere else.
+ConvPlan az_conv_g8_plan(const ConvBf16Args& a, int mode) { return conv_plan_g8(conv_shape(a), mode, g_conv_flags); }
+ConvPlan az_conv_nhwc16_plan(const ConvBf16Args& a, int mode) { return conv_plan_nhwc16(conv_shape(a), mode, g_conv_flags); }
+ConvPlan az_conv_x3_plan(const ConvBf16Args& a) { return conv_plan_x3(conv_shape(a), g_conv_flags); }
+
+int az_conv_g8_launch(const ConvBf16Args& a_in, int mode, hipStream_t st) {
+    ConvBf16Args a = a_in;
+    a.flags = g_conv_flags;        // conv3x3_v7 reads CONV_F_V7_PER_TAP / CONV_F_V7_OLD_TAIL itself
+    if (a.a_tail == 0) a.a_tail = (size_t)a.M * a.C * 2;
+    return az_conv_launch(az_conv_g8_plan(a, mode), a, st);
+}
+
+int az_conv_nhwc16_launch(const ConvBf16Args& a, int mode, hipStream_t st) {
+    return az_conv_launch(az_conv_nhwc16_plan(a, mode), a, st);
+}
+
+// the plan's shape checks plus the planes the x3 kernels read and write without asking
+int az_conv_v7x3_launch(const ConvBf16Args& a, hipStream_t st) {
+    if (!a.Ahi || !a.Alo || !a.Bblk || !a.Bblk_lo || !a.Chi || !a.Clo) return -1;
+    if (a.pt == 2 && !a.oscale) return -1;                // fp16 pieces: the weights' per-channel scale
+    return az_conv_launch(az_conv_x3_plan(a), a, st);
 }

@@ -190,7 +190,7 @@ __device__ __forceinline__ void static_for(Fn&& f) {
     }
 }
 
-// Tile geometries (one board per tile unless DENSE):
+// Tile geometries (GEO_*, conv_plan.h; one board per tile unless DENSE):
 //  GEO_PAD   outputs on an HB x (HB+2) grid: tap (dy, dx) of output row q is halo row q + dy*WG + dx
 //            of the zero-padded (HB+2)^2 halo (two dead columns per grid row; 15x15: 225 of 256 rows live)
 //  GEO_SLIM  outputs on an HB x (HB+1) grid over a halo of HB+2 rows of HB+1 columns whose column 0
@@ -202,7 +202,6 @@ __device__ __forceinline__ void static_for(Fn&& f) {
 //            through phi copies and spill)
 //  GEO_DENSE 256 consecutive pixels of the batch, taps that leave the board zeroed in the fragments
 //  TM        DENSE only: output rows per tile (256; 128 / 64 for small batches, conv3x3_v7 only)
-enum { GEO_PAD = 0, GEO_SLIM = 1, GEO_DENSE = 2 };
 template <int HB, int GEO, int TM = 256>
 struct Geom7 {
     static constexpr bool DENSE = GEO == GEO_DENSE, SLIM = GEO == GEO_SLIM;
@@ -461,7 +460,7 @@ __global__ __launch_bounds__(256, RG == 3 ? 3 : 2) void conv3x3_v7(ConvBf16Args 
     // vmcnt counts the halo's DMA pieces, the residual pieces and the weight loads together in issue
     // order; the budget before the chunk barrier is a compile-time constant (see there).
     if constexpr (ROWS) {
-        if (!(p.flags & 0x2000)) {
+        if (!(p.flags & CONV_F_V7_PER_TAP)) {
             constexpr int NF = GM::NFRAG, NFR = NF + 2;   // 15 output fragments, 17 fragment rows of the halo
             static_assert(NF == 15 && NRB == 5 && (NFR * 16 + 2) <= GM::TROWS, "row-streamed geometry");
             f32x4v acc[NF][2];
@@ -517,7 +516,7 @@ __global__ __launch_bounds__(256, RG == 3 ? 3 : 2) void conv3x3_v7(ConvBf16Args 
             // which the last chunk (reading buffer (NCH - 1) & 1) leaves idle; [row][wave][1 KB].
             constexpr int RR0 = 10;
             static_assert(2 * A_BUF + RR0 * R_ROW <= LDS && (NF - RR0) * R_ROW <= A_BUF && NF - RR0 <= NRB, "residual images");
-            const bool tail_old = (p.flags & 0x4000) != 0;
+            const bool tail_old = (p.flags & CONV_F_V7_OLD_TAIL) != 0;
             const bool resid = p.Rhi && !tail_old;
             const __amdgpu_buffer_rsrc_t rsR = __builtin_amdgcn_make_buffer_rsrc((void*)p.Rhi, (short)0, 0x7fffffff, 0x00020000);
             uint8_t* const r_lo = lds + 2 * A_BUF + wave * 1024;
@@ -1565,160 +1564,77 @@ extern "C" int az_diag_v7_stamps(int sel, unsigned long long* st, unsigned* hw, 
 #endif
 }
 
+// Executing a plan (conv_plan.h): each helper maps the plan's runtime fields to the one instantiation
+// they name and launches it on the plan's grid; a combination without an instantiation is an error.
 template <int HB, int GEO, int TM = 256, int RG = 4>
-static void v7_launch_g(const ConvBf16Args& a, int mode, hipStream_t st) {
-    const int boards = a.M / (HB * HB);
-    const int tiles = GEO == GEO_DENSE ? (boards * HB * HB + TM - 1) / TM : boards;
-    const int grid = (tiles + 7) / 8 * 8 * (a.N / 128);   // XCD-aware tile/half mapping: whole groups of 8
-    // diagnostic conv flag 0x100000: 64 KB of unused dynamic LDS per block (fewer blocks per CU)
-    const unsigned dyn = (a.flags & 0x100000) ? 65536u : 0u;
-    if (mode == 2) hipLaunchKernelGGL((conv3x3_v7<2, HB, GEO, TM, RG>), dim3(grid), dim3(256), dyn, st, a);
-    else hipLaunchKernelGGL((conv3x3_v7<1, HB, GEO, TM, RG>), dim3(grid), dim3(256), dyn, st, a);
+static int v7_launch_g(const ConvPlan& p, const ConvBf16Args& a, hipStream_t st) {
+    if (p.mode == 2) hipLaunchKernelGGL((conv3x3_v7<2, HB, GEO, TM, RG>), dim3(p.grid), dim3(p.block), 0, st, a);
+    else if (p.mode == 1) hipLaunchKernelGGL((conv3x3_v7<1, HB, GEO, TM, RG>), dim3(p.grid), dim3(p.block), 0, st, a);
+    else return -1;
+    return 0;
 }
-// DENSE boards: the tile rows (256 / 128 / 64) for this launch -- small batches take smaller tiles
-// so one round of blocks covers the CUs (az_conv_v7_tm; flag bits 0x70000 force 256 / 128 / 64 / 192)
+// conv3x3_v7 of one board: DENSE tiles of 256 / 192 rows on the 4-slot ring, of 128 / 64 rows on
+// either ring; 15x15 has the PAD and SLIM tiles besides
 template <int HB>
-static void v7_launch_dense(const ConvBf16Args& a, int mode, hipStream_t st) {
-    const bool r3 = az_conv_v7_ring(a) == 3;
-    switch (az_conv_v7_tm(a)) {
-        case 64: if (r3) v7_launch_g<HB, GEO_DENSE, 64, 3>(a, mode, st); else v7_launch_g<HB, GEO_DENSE, 64>(a, mode, st); break;
-        case 128: if (r3) v7_launch_g<HB, GEO_DENSE, 128, 3>(a, mode, st); else v7_launch_g<HB, GEO_DENSE, 128>(a, mode, st); break;
-        case 192: v7_launch_g<HB, GEO_DENSE, 192>(a, mode, st); break;
-        default: v7_launch_g<HB, GEO_DENSE, 256>(a, mode, st); break;
+static int v7_launch(const ConvPlan& p, const ConvBf16Args& a, hipStream_t st) {
+    if (p.geo == GEO_DENSE) {
+        switch (p.tm * 10 + p.ring) {
+            case 643: return v7_launch_g<HB, GEO_DENSE, 64, 3>(p, a, st);
+            case 644: return v7_launch_g<HB, GEO_DENSE, 64>(p, a, st);
+            case 1283: return v7_launch_g<HB, GEO_DENSE, 128, 3>(p, a, st);
+            case 1284: return v7_launch_g<HB, GEO_DENSE, 128>(p, a, st);
+            case 1924: return v7_launch_g<HB, GEO_DENSE, 192>(p, a, st);
+            case 2564: return v7_launch_g<HB, GEO_DENSE, 256>(p, a, st);
+            default: return -1;
+        }
     }
-}
-
-// The DENSE tile rows of a conv3x3_v7 launch: 256 unless the launch is under two rounds of blocks
-// (two blocks per CU), where 192 / 128 / 64-row tiles spread the work over more CUs.  Conv flag bits
-// 0x70000 force 256 (1) / 128 (2) / 64 (3) / 192 (4) for A/B measurement.
-int az_conv_v7_tm(const ConvBf16Args& a) {
-    const int force = (a.flags >> 16) & 7;
-    if (force) return force == 1 ? 256 : force == 2 ? 128 : force == 3 ? 64 : 192;
-    const long rows = (long)a.M;
-    const int halves = a.N / 128;
-    const long boards = rows / ((long)a.H * a.W);
-    auto blocks = [&](int tm) { return ((rows + tm - 1) / tm + 7) / 8 * 8 * halves; };
-    // below 1024 boards (g8_choice's small-batch branch) 19x19 -- and 13x13 once 128-row tiles fill
-    // the CUs -- take 128-row tiles on the 3-slot ring (az_conv_v7_ring) at every size, including
-    // those whose 256-row tiles would make 1024 blocks: 19x19 128 boards 0.0594 ms (192-row: 0.0620),
-    // 256: 0.1106 (0.1160), 384: 0.1645 (256-row: 0.1887), 512: 0.2111 (0.2268; v6 0.2107), 768:
-    // 0.3085 (0.3392) (profiles/r05_small_batch_ring3.txt)
-    if (boards < 1024 && (a.H == 19 || (a.H == 13 && blocks(128) >= 512))) return 128;
-    if (blocks(256) >= 1024) return 256;
-    if (blocks(128) >= 512) return 128;
-    return 64;
-}
-
-// Weight-ring slots of a DENSE conv3x3_v7 launch with tiles under 256 rows: 3 (three blocks per CU)
-// for the automatic 128-row tiles or with conv flag 0x80000, else 4 (two blocks per CU).  128-row
-// tiles, 4 -> 3 slots: 19x19 128 boards 0.0620 (192-row) -> 0.0594 ms, 13x13 256 0.0709 -> 0.0592,
-// 13x13 512 0.1230 -> 0.1092, 9x9 512 0.0700 -> 0.0578, 8x8 512 0.0444 -> 0.0436; the 64-row tiles
-// measured within +-2 % (8x8 128 0.0217 vs 0.0221, 9x9 256 0.0360 vs 0.0353) and keep 4
-// (profiles/r05_small_batch_ring3.txt)
-int az_conv_v7_ring(const ConvBf16Args& a) {
-    const int tm = az_conv_v7_tm(a);
-    if (tm > 128) return 4;
-    if (a.flags & 0x80000) return 3;
-    return (tm == 128 && !((a.flags >> 16) & 7)) ? 3 : 4;
-}
-
-// true when conv3x3_v7 takes this layer
-bool az_conv_v7_supported(const ConvBf16Args& a) {
-    if (!a.relu || a.Cf || a.Clo) return false;
-    return az_conv_v7_shape_supported(a.H, a.W, a.C, a.N, a.a_tail);
-}
-
-// conv3x3_v7x3 (AZ_PREC_BF16X3 on the g8 hi / lo planes): same shapes as conv3x3_v7, plus the lo
-// planes of the input and the weights and both output planes; a residual needs both of its planes
-bool az_conv_v7x3_supported(const ConvBf16Args& a) {
-    if (!a.relu || a.Cf || a.Cq || a.Rq) return false;
-    if (!a.Ahi || !a.Alo || !a.Bblk || !a.Bblk_lo || !a.Chi || !a.Clo || (!a.Rhi) != (!a.Rlo)) return false;
-    if (a.pt == 2 && !a.oscale) return false;             // fp16 pieces: the weights' per-channel scale
-    return a.a_tail >= (size_t)a.M * a.C * 2 && az_conv_v7_shape_supported(a.H, a.W, a.C, a.N, a.a_tail);
+    if constexpr (HB == 15) {
+        if (p.tm == 256 && p.ring == 4 && p.geo == GEO_PAD) return v7_launch_g<15, GEO_PAD>(p, a, st);
+        if (p.tm == 256 && p.ring == 4 && p.geo == GEO_SLIM) return v7_launch_g<15, GEO_SLIM>(p, a, st);
+    }
+    return -1;
 }
 
 template <int HB, int GEO>
-static void v7x3_launch_g(const ConvBf16Args& a, hipStream_t st) {
-    const int boards = a.M / (HB * HB);
-    const int tiles = GEO == GEO_DENSE ? (boards * HB * HB + 255) / 256 : boards;
-    const int grid = (tiles + 7) / 8 * 8 * (a.N / 128);
-    if (a.pt == 2) hipLaunchKernelGGL((conv3x3_v7x3<HB, GEO, 2>), dim3(grid), dim3(256), 0, st, a);
-    else hipLaunchKernelGGL((conv3x3_v7x3<HB, GEO, 1>), dim3(grid), dim3(256), 0, st, a);
-}
-
-// first-round stagger (ns; az_diag_set_v9_stagger): 32 us measured best of 0 / 8 / 16 / 32 / 64 us,
-// -0.8 % per C3 launch, -0.7 % C4 (profiles/r04_v9x3_stagger.txt); only on launches of >= 1024 blocks
-// (several rounds), where a one-off delay of the last-started CU is amortised
-static int g_v9_stagger = 32000;
-extern "C" int az_diag_set_v9_stagger(int ns) { g_v9_stagger = ns; return 0; }
-// conv3x3_v9x3 variants (A/B measurement, bf16 pieces): flag 0x20000000 puts the tap barrier at the
-// tap start instead of after unit U0, 0x40000000 keeps the SLIM tile's dead 16th fragment in waves
-// 4-7.  fp16 pieces (AZ_PREC_F16X3) run the default variant only.
-template <int HB, int GEO>
-static void v9x3_launch_g(const ConvBf16Args& a, hipStream_t st) {
-    const int boards = a.M / (HB * HB);
-    const int tiles = GEO == GEO_DENSE ? (boards * HB * HB + 255) / 256 : boards;
-    const int f = az_conv_flags(), var = ((f & 0x20000000) ? 0 : 1) | ((f & 0x40000000) ? 0 : 2);
-    const dim3 grid(tiles * (a.N / 256)), block(512);
-    ConvBf16Args b = a;
-    b.stagger = tiles * (a.N / 256) >= 1024 ? g_v9_stagger : 0;
-    if (a.pt == 2) {
-        hipLaunchKernelGGL((conv3x3_v9x3<HB, GEO, 3, 2>), grid, block, 0, st, b);
-        return;
-    }
-    switch (var) {
-        case 0: hipLaunchKernelGGL((conv3x3_v9x3<HB, GEO, 0, 1>), grid, block, 0, st, b); break;
-        case 1: hipLaunchKernelGGL((conv3x3_v9x3<HB, GEO, 1, 1>), grid, block, 0, st, b); break;
-        case 2: hipLaunchKernelGGL((conv3x3_v9x3<HB, GEO, 2, 1>), grid, block, 0, st, b); break;
-        default: hipLaunchKernelGGL((conv3x3_v9x3<HB, GEO, 3, 1>), grid, block, 0, st, b); break;
-    }
-}
-
-// conv3x3_v9x3 takes every bf16x3 trunk layer with N % 256 == 0 unless conv flag 0x10000000
-// selects conv3x3_v7x3 (A/B measurement)
-static bool x3_wide(const ConvBf16Args& a) { return a.N % 256 == 0 && !(az_conv_flags() & 0x10000000); }
-
-// the kernel az_conv_v7x3_launch takes (bench.py's roofline label)
-int az_conv_x3_name(const ConvBf16Args& a, char* out, int len) {
-    if (!az_conv_v7_shape_supported(a.H, a.W, a.C, a.N, a.a_tail)) return -1;
-    snprintf(out, len, "%s<%d, %s%s>", x3_wide(a) ? "conv3x3_v9x3" : "conv3x3_v7x3", a.H, a.H == 15 ? "SLIM" : "DENSE",
-             a.pt == 2 ? ", f16" : "");
+static int v7x3_launch_g(const ConvPlan& p, const ConvBf16Args& a, hipStream_t st) {
+    if (p.pt == 2) hipLaunchKernelGGL((conv3x3_v7x3<HB, GEO, 2>), dim3(p.grid), dim3(p.block), 0, st, a);
+    else hipLaunchKernelGGL((conv3x3_v7x3<HB, GEO, 1>), dim3(p.grid), dim3(p.block), 0, st, a);
     return 0;
 }
 
-// 15x15 boards on the SLIM tile, every other board DENSE (as conv3x3_v7's defaults)
-int az_conv_v7x3_launch(const ConvBf16Args& a, hipStream_t st) {
-    if (!az_conv_v7x3_supported(a)) return -1;
-    if (x3_wide(a)) {
-        switch (a.H) {
-            case 8: v9x3_launch_g<8, GEO_DENSE>(a, st); return 0;
-            case 9: v9x3_launch_g<9, GEO_DENSE>(a, st); return 0;
-            case 13: v9x3_launch_g<13, GEO_DENSE>(a, st); return 0;
-            case 19: v9x3_launch_g<19, GEO_DENSE>(a, st); return 0;
-            default: v9x3_launch_g<15, GEO_SLIM>(a, st); return 0;
-        }
+// first-round stagger (ns; az_diag_set_v9_stagger): 32 us measured best of 0 / 8 / 16 / 32 / 64 us,
+// -0.8 % per C3 launch, -0.7 % C4 (profiles/r04_v9x3_stagger.txt); on the launches the plan names
+static int g_v9_stagger = 32000;
+extern "C" int az_diag_set_v9_stagger(int ns) { g_v9_stagger = ns; return 0; }
+template <int HB, int GEO>
+static int v9x3_launch_g(const ConvPlan& p, const ConvBf16Args& a, hipStream_t st) {
+    const dim3 grid(p.grid), block(p.block);
+    ConvBf16Args b = a;
+    b.stagger = p.stagger ? g_v9_stagger : 0;
+    if (p.pt == 2) {
+        if (p.var != 3) return -1;
+        hipLaunchKernelGGL((conv3x3_v9x3<HB, GEO, 3, 2>), grid, block, 0, st, b);
+        return 0;
     }
-    switch (a.H) {
-        case 8: v7x3_launch_g<8, GEO_DENSE>(a, st); return 0;
-        case 9: v7x3_launch_g<9, GEO_DENSE>(a, st); return 0;
-        case 13: v7x3_launch_g<13, GEO_DENSE>(a, st); return 0;
-        case 19: v7x3_launch_g<19, GEO_DENSE>(a, st); return 0;
-        default: v7x3_launch_g<15, GEO_SLIM>(a, st); return 0;
+    switch (p.var) {
+        case 0: hipLaunchKernelGGL((conv3x3_v9x3<HB, GEO, 0, 1>), grid, block, 0, st, b); return 0;
+        case 1: hipLaunchKernelGGL((conv3x3_v9x3<HB, GEO, 1, 1>), grid, block, 0, st, b); return 0;
+        case 2: hipLaunchKernelGGL((conv3x3_v9x3<HB, GEO, 2, 1>), grid, block, 0, st, b); return 0;
+        case 3: hipLaunchKernelGGL((conv3x3_v9x3<HB, GEO, 3, 1>), grid, block, 0, st, b); return 0;
+        default: return -1;
     }
 }
 
-// geo15: the 15x15 tile geometry (GEO_PAD / GEO_SLIM / GEO_DENSE); other boards are DENSE
-int az_conv_v7_launch(const ConvBf16Args& a, int mode, int geo15, hipStream_t st) {
-    if (!az_conv_v7_supported(a)) return -1;
-    switch (a.H) {
-        case 8: v7_launch_dense<8>(a, mode, st); return 0;
-        case 9: v7_launch_dense<9>(a, mode, st); return 0;
-        case 13: v7_launch_dense<13>(a, mode, st); return 0;
-        case 19: v7_launch_dense<19>(a, mode, st); return 0;
-        default:
-            if (geo15 == GEO_DENSE) v7_launch_dense<15>(a, mode, st);
-            else if (geo15 == GEO_PAD) v7_launch_g<15, GEO_PAD>(a, mode, st);
-            else v7_launch_g<15, GEO_SLIM>(a, mode, st);
-            return 0;
-    }
+// az_conv_launch's half for the kernels of this file (CONV_V7 / CONV_V7X3 / CONV_V9X3)
+int az_conv_launch_v7(const ConvPlan& p, const ConvBf16Args& a, hipStream_t st) {
+    return az_conv_board_dispatch(p.board, [&](auto hb) -> int {
+        constexpr int HB = decltype(hb)::value;
+        constexpr int GEO_X3 = HB == 15 ? GEO_SLIM : GEO_DENSE;   // the x3 kernels' one tile per board
+        switch (p.kernel) {
+            case CONV_V7: return v7_launch<HB>(p, a, st);
+            case CONV_V7X3: return p.geo == GEO_X3 && p.tm == 256 ? v7x3_launch_g<HB, GEO_X3>(p, a, st) : -1;
+            case CONV_V9X3: return p.geo == GEO_X3 && p.tm == 256 ? v9x3_launch_g<HB, GEO_X3>(p, a, st) : -1;
+            default: return -1;
+        }
+    });
 }

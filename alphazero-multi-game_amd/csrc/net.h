@@ -1,10 +1,13 @@
 // net.h -- launch interface of the ConvNet kernels (net_kernels.hip, conv_bf16.hip, conv_v7.hip,
 // smallnet.hip): the one declaration of every launcher, included by the file that defines it and
-// by every file that calls it.  The shape predicates the launchers guard with are in net_plan.h.
+// by every file that calls it.  The shape predicates the launchers guard with are in net_plan.h and
+// conv_plan.h, which also decides every trunk conv launch.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
+#include <type_traits>
 
+#include "conv_plan.h"
 #include "net_plan.h"
 
 enum { ACT_NONE = 0, ACT_RELU = 1, ACT_TANH = 2 };
@@ -122,12 +125,37 @@ void az_launch_rec_planes(const uint8_t* rec, float* dst, const int* eval_games,
                           hipStream_t st);
 
 // ---- conv_bf16.hip: the 3x3 trunk convs on 16-bit operands, layout conversions, g8 pool
-int az_conv_flags();                  // kernel variant bits (az_diag_set_conv_flags)
-void az_conv_bf16_launch_v(const ConvBf16Args& a, bool split, hipStream_t st);
-int az_conv_bf16_name(const ConvBf16Args& a, int mode, char* out, int len);
-void az_conv_v4_launch(const ConvBf16Args& a, int mode, hipStream_t st);
+int az_conv_flags();                  // kernel variant bits (az_diag_set_conv_flags; CONV_F_*, conv_plan.h)
+// what conv_plan.h reads of a launch
+inline ConvShape conv_shape(const ConvBf16Args& a) {
+    return {a.H, a.W, a.C, a.N, a.M, a.a_tail, a.rows_per_sample, a.relu, a.pt,
+            a.Cf != nullptr, a.Clo != nullptr, a.Cq != nullptr, a.Rq != nullptr, a.Rhi != nullptr, a.Rlo != nullptr};
+}
+// One trunk conv per family.  az_conv_*_plan: conv_plan.h's plan of (conv_shape(a), mode, az_conv_flags()),
+// what az_net_trunk_kernel names; az_conv_*_launch hands that plan to az_conv_launch (-1 when no
+// kernel takes the shape).  mode: 0 bf16 hi + lo, 1 bf16, 2 fp16; the x3 family's pieces: a.pt.
+ConvPlan az_conv_g8_plan(const ConvBf16Args& a, int mode);
+ConvPlan az_conv_nhwc16_plan(const ConvBf16Args& a, int mode);
+ConvPlan az_conv_x3_plan(const ConvBf16Args& a);
 int az_conv_g8_launch(const ConvBf16Args& a, int mode, hipStream_t st);
-int az_conv_g8_name(const ConvBf16Args& a, int mode, char* out, int len);
+int az_conv_nhwc16_launch(const ConvBf16Args& a, int mode, hipStream_t st);
+int az_conv_v7x3_launch(const ConvBf16Args& a, hipStream_t st);
+// Executes a plan: the one place a plan's runtime fields become template arguments.  A plan that
+// names a kernel, board, tile or variant without an instantiation is an error (-1), never a fallback.
+int az_conv_launch(const ConvPlan& p, const ConvBf16Args& a, hipStream_t st);
+int az_conv_launch_v7(const ConvPlan& p, const ConvBf16Args& a, hipStream_t st);   // conv_v7.hip's kernels
+// f(std::integral_constant<int, board>) for a board with instantiations, -1 for any other
+template <typename F>
+int az_conv_board_dispatch(int board, F&& f) {
+    switch (board) {
+        case 8: return f(std::integral_constant<int, 8>{});
+        case 9: return f(std::integral_constant<int, 9>{});
+        case 13: return f(std::integral_constant<int, 13>{});
+        case 15: return f(std::integral_constant<int, 15>{});
+        case 19: return f(std::integral_constant<int, 19>{});
+        default: return -1;
+    }
+}
 void az_launch_to_g8(const float* in, uint16_t* hi, int8_t* q, int C, int HW, const int* m_limit, int maxB, int mode,
                      hipStream_t st, int Cout = 0);
 void az_launch_rec_to_g8(const uint8_t* rec, const int* gidx, uint16_t* hi, int go, int bs, const int* m_limit, int maxB,
@@ -143,12 +171,3 @@ void az_launch_pool_g8(const uint16_t* hi, const int8_t* q, float* out, int B, i
 size_t az_device_lds_limit();         // LDS per workgroup of the current device (az_pool_heads_supported's limit)
 int az_launch_pool_heads_g8(const uint16_t* hi, const int8_t* q, const float* Wt, const float* bias, float* out, int B,
                             int C, int H, int P, int N, const int* m_limit, int mode, hipStream_t st);
-
-// ---- conv_v7.hip: conv3x3_v7 (taken by az_conv_g8_launch) and the x3 trunk convs (v7x3 / v9x3)
-bool az_conv_v7_supported(const ConvBf16Args& a);
-int az_conv_v7_launch(const ConvBf16Args& a, int mode, int geo15, hipStream_t st);
-int az_conv_v7_tm(const ConvBf16Args& a);     // DENSE boards: the tile rows (256 / 128 / 64) for this launch
-int az_conv_v7_ring(const ConvBf16Args& a);
-bool az_conv_v7x3_supported(const ConvBf16Args& a);
-int az_conv_v7x3_launch(const ConvBf16Args& a, hipStream_t st);
-int az_conv_x3_name(const ConvBf16Args& a, char* out, int len);

@@ -79,6 +79,7 @@ float* trunk_rw(az_net* n, int trunk, int B, const int* nb, hipStream_t st) {
     const az_net_desc& d = n->d;
     const int F = d.channels, H = d.board_size, HW = n->HW, rows = B * HW, R = F / 16;
     float* x = n->h0;
+    bool conv_err = false;
     for (const RwBlock& blk : n->rwb) {
         const azrw::Plan& pl = blk.plan;
         auto node = [&](int v, const float* in) {
@@ -107,8 +108,7 @@ float* trunk_rw(az_net* n, int trunk, int B, const int* nb, hipStream_t st) {
                     a.Bhi = nd.c1.Wh16; a.Bblk = nd.c1.Wbk_h;
                     c.Bhi = nd.c2.Wh16; c.Bblk = nd.c2.Wbk_h;
                 }
-                az_conv_v4_launch(a, x3 ? 0 : 2, st);
-                az_conv_v4_launch(c, x3 ? 0 : 2, st);
+                if (az_conv_nhwc16_launch(a, x3 ? 0 : 2, st) || az_conv_nhwc16_launch(c, x3 ? 0 : 2, st)) conv_err = true;
             }
             az_launch_se_residual(n->rw_t2, in, n->rw_out[v], nd.w1, nd.b1, nd.w2, nd.b2, B, HW, F, R, nb, st);
         };
@@ -128,7 +128,7 @@ float* trunk_rw(az_net* n, int trunk, int B, const int* nb, hipStream_t st) {
         }
         x = y;
     }
-    return x;
+    return conv_err ? nullptr : x;
 }
 
 // Diagnostic (az_diag_set_poison): with a byte value >= 0, every activation / workspace buffer of a
@@ -334,14 +334,12 @@ float* trunk_nhwc16(az_net* n, int B, const int* nb, hipStream_t st) {
             // fp16 conv operands, fp32 residual stream (an fp16 stream doubles the logit error)
             b2.Rf = d.residual ? h : nullptr;
             b2.Cf = other;
-            az_conv_v4_launch(a, 2, st);
-            az_conv_v4_launch(b2, 2, st);
+            if (az_conv_nhwc16_launch(a, 2, st) || az_conv_nhwc16_launch(b2, 2, st)) return nullptr;
             std::swap(h, other);
         } else {
             if (d.residual) { b2.Rhi = n->hh[cur]; b2.Rlo = split ? n->hl[cur] : nullptr; }
             b2.Cf = (i == d.blocks - 1) ? other : nullptr;
-            az_conv_bf16_launch_v(a, split, st);
-            az_conv_bf16_launch_v(b2, split, st);
+            if (az_conv_nhwc16_launch(a, split ? 0 : 1, st) || az_conv_nhwc16_launch(b2, split ? 0 : 1, st)) return nullptr;
         }
         cur ^= 1;
     }
@@ -382,6 +380,7 @@ int net_forward(az_net* n, const float* x0, int B, const int* nb, float* logits,
         default: h = trunk_rw(n, pl.trunk, B, nb, st); break;
     }
     if (r) return r;
+    if (!g8 && !h) return az_fail(AZ_ERR_ARG, "trunk conv: unsupported shape");
     if (sampled) n->pc.stamp(st);
 
     // the tail -- pool and both head 1x1 convs: one launch on the g8 paths (k_pool_heads_g8, bitwise
@@ -666,15 +665,16 @@ int az_net_trunk_kernel(az_net* n, char* name, int len) {
     a.pt = prec == AZ_PREC_F16X3 ? 2 : 1;
     int r = 0;
     switch (pl.trunk) {
+        // the rand-wire labels carry v4's schedule argument, the NHWC16 ones do not: kept as they are
         case NET_TRUNK_RW_V4_FP16: snprintf(name, len, "conv3x3_v4<2, 128, 1>"); break;
         case NET_TRUNK_RW_V4_X3: snprintf(name, len, "conv3x3_v4<0, 128, 0>"); break;
         case NET_TRUNK_SMALL:   // as rocprofv3 names them
             if (f16) snprintf(name, len, "k_smallnet_g<%d, 8, %s>", d.board_size, res);
             else snprintf(name, len, "k_smallnet_x3<%d, 8, %s, %d>", d.board_size, res, a.pt);
             break;
-        case NET_TRUNK_G8X3: r = az_conv_x3_name(a, name, len); break;
-        case NET_TRUNK_G8: r = az_conv_g8_name(a, f16 ? 2 : 1, name, len); break;
-        case NET_TRUNK_NHWC16: r = az_conv_bf16_name(a, f16 ? 2 : prec == AZ_PREC_BF16X3 ? 0 : 1, name, len); break;
+        case NET_TRUNK_G8X3: r = conv_plan_name(az_conv_x3_plan(a), name, len); break;
+        case NET_TRUNK_G8: r = conv_plan_name(az_conv_g8_plan(a, f16 ? 2 : 1), name, len); break;
+        case NET_TRUNK_NHWC16: r = conv_plan_name(az_conv_nhwc16_plan(a, f16 ? 2 : prec == AZ_PREC_BF16X3 ? 0 : 1), name, len); break;
         default: snprintf(name, len, "gemm_f32"); break;
     }
     return r ? az_fail(AZ_ERR_ARG, "no trunk kernel for this net") : 0;

@@ -5,29 +5,16 @@
 // tests/test_net_plan_cpu.py reads the whole table without a GPU.
 //
 // The plan picks the kernel family; the instantiation for one launch (v6 / v7 by the batch, the v7
-// tile rows and ring, v3 / v4 / conv3x3_bf16, v9x3 / v7x3 by the width, v4's one-board variant) stays
-// with the launchers in conv_bf16.hip / conv_v7.hip.
+// tile rows and ring, v3 / v4 / conv3x3_bf16, v9x3 / v7x3 by the width, v4's one-board variant) is
+// conv_plan.h's, which also holds the conv kernels' shape predicates and the conv flag bits.
 #pragma once
 #include <cstddef>
 #include <cstdio>
 
 #include "../../include/az_engine.h"
+#include "conv_plan.h"
 
-// zeroed 16-bit elements behind every g8 activation buffer (512 KB): the v6 / v7 convs point the DMA
-// of halo padding rows there
-constexpr size_t AZ_ACT_TAIL = 262144;
-
-// ---- shape predicates of the kernels (the launchers add their pointer checks)
-
-// boards with a G8Geom instantiation
-inline bool az_g8_board(int H) { return H == 8 || H == 9 || H == 13 || H == 15 || H == 19; }
-// the g8 trunk (conv3x3_v5 at 15x15 / v6 / v7): square boards, 128-channel output halves, 16-channel
-// chunks (v5, 15x15) or 32 (v6)
-inline bool az_conv_g8_supported(int H, int W, int C, int N) {
-    if (H != W || !az_g8_board(H) || N % 128 != 0 || C < 16) return false;
-    return H == 15 ? C % 16 == 0 : C % 32 == 0;
-}
-inline bool az_conv_v4_supported(int H, int W, int C, int N) { return H == 15 && W == 15 && C % 16 == 0 && N % 64 == 0; }
+// ---- shape predicates of the fused kernels (the conv kernels': conv_plan.h)
 
 // k_smallnet: 15x15, 64 filters, 16 input planes, heads of 32 channels; its biases sit in LDS rows
 // (smallnet.hip asserts both constants against SF and SmGeom<15>::MAXL)
@@ -44,17 +31,6 @@ inline bool az_smallnet_supported(int H, int C, int cin_pad, int pool, int head_
 inline size_t az_pool_heads_lds(int H) { return ((size_t)H * H * 36 + 2 * 64 * 33) * sizeof(float); }
 inline bool az_pool_heads_supported(int C, int H, int P, int N, size_t lds_limit) {
     return C % 32 == 0 && P * P <= 64 && N == 64 && H * H <= 361 && az_pool_heads_lds(H) <= lds_limit;
-}
-
-// conv3x3_v6 / v7 / v7x3 / v9x3 address activations and weights through 32-bit buffer ranges, and
-// their padding offset walks C / 32 chunk steps of 4 HW 16 B into the zeroed tail
-inline bool az_act_range_ok(size_t a_tail) { return a_tail + AZ_ACT_TAIL * 2 < ((size_t)1 << 31); }
-inline bool az_weight_range_ok(int C, int N) { return (size_t)9 * C * N * 2 < ((size_t)1 << 31); }
-inline bool az_tail_reach_ok(int H, int C) { return (size_t)(C / 32) * 4 * ((size_t)H * H) * 16 + 16 <= AZ_ACT_TAIL * 2; }
-// the shapes conv3x3_v7 and the x3 convs (v7x3 / v9x3) take; a_tail: bytes in front of the zeroed tail
-inline bool az_conv_v7_shape_supported(int H, int W, int C, int N, size_t a_tail) {
-    return H == W && az_g8_board(H) && C % 64 == 0 && N % 128 == 0 && az_act_range_ok(a_tail) && az_tail_reach_ok(H, C) &&
-           az_weight_range_ok(C, N);
 }
 
 // ---- the route
@@ -171,8 +147,8 @@ inline void refusal(const NetShape& s, int prec, NetPlan& p) {
 
 }  // namespace net_plan_detail
 
-// conv_flags: az_conv_flags() (0x400000 keeps k_pool_g8 + the head GEMMs, 0x08000000 the f32
-// k_fc_heads); lds_limit: the device's LDS per workgroup.
+// conv_flags: az_conv_flags() (CONV_F_KEEP_POOL keeps k_pool_g8 + the head GEMMs, CONV_F_FC_F32 the
+// f32 k_fc_heads); lds_limit: the device's LDS per workgroup.
 inline NetPlan net_plan(const NetShape& s, int prec, int conv_flags, size_t lds_limit) {
     NetPlan p{};
     net_plan_detail::refusal(s, prec, p);
@@ -205,7 +181,7 @@ inline NetPlan net_plan(const NetShape& s, int prec, int conv_flags, size_t lds_
     if (prec == AZ_PREC_F16X3 && p.trunk != NET_TRUNK_G8X3 && p.trunk != NET_TRUNK_SMALL)
         p.no_forward = "AZ_PREC_F16X3: no fp16-piece trunk for this shape";
     p.tail_fused = (p.trunk == NET_TRUNK_G8 || p.trunk == NET_TRUNK_G8X3) && HK % 32 == 0 &&
-                   az_pool_heads_supported(F, H, s.pool, 2 * s.head_channels, lds_limit) && !(conv_flags & 0x400000);
+                   az_pool_heads_supported(F, H, s.pool, 2 * s.head_channels, lds_limit) && !(conv_flags & CONV_F_KEEP_POOL);
     p.head_conv_fused = p.trunk != NET_TRUNK_SMALL && !p.tail_fused && HK % 32 == 0;
     // split-operand FC products at 5x the f32 MFMA rate: the throughput precisions (fp16 / bf16 trunk)
     // in bf16 pieces (~2^-16 per product; their trunk error is 30x larger), AZ_PREC_F16X3 in scaled fp16
@@ -213,7 +189,7 @@ inline NetPlan net_plan(const NetShape& s, int prec, int conv_flags, size_t lds_
     // add ~2.5e-5 at trained-scale logits).  Below 512 boards of capacity the f32 pair is the faster
     // one (C2, 256 boards: k_fc_heads 10.6 us vs k_fc_heads_x3 12.0 -- both latency-bound chains of L2
     // round trips at 0.5 GFLOP)
-    const bool fx = !(conv_flags & 0x08000000) && s.max_batch >= 512;
+    const bool fx = !(conv_flags & CONV_F_FC_F32) && s.max_batch >= 512;
     p.heads = HK % 32 ? NET_HEADS_GENERIC
               : fx && h16 ? NET_HEADS_X3_BF16 : fx && prec == AZ_PREC_F16X3 ? NET_HEADS_X3_FP16 : NET_HEADS_F32;
     return p;
