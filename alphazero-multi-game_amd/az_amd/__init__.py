@@ -12,6 +12,9 @@ Reference surfaces mirrored (paths relative to the reference root):
                     generateGames() with the playSingleGame move loop and temperature schedule.
   Dataset           alphazero::selfplay::Dataset (src/selfplay/dataset.cpp): extractExamples with the
                     8-fold augmentation on device, getBatch, shuffle, getRandomSubset, save/load.
+Beyond the reference:
+  ReplayBuffer      az_replay_*: a device-resident ring of action-space training targets that self-play
+                    fills (ParallelMCTS.attachReplay) and a trainer samples.
 """
 import ctypes
 from dataclasses import dataclass, field
@@ -19,10 +22,10 @@ from dataclasses import dataclass, field
 import numpy as np
 
 from ._lib import (AZ_GO_RULES_SET, AZ_MAX_LEAVES, GomokuRules, AZ_SEL_PROGRESSIVE_BIAS, AZ_SEL_PUCT, AZ_SEL_RAVE, AZ_SEL_UCB, SearchOpts, AZ_EVAL_CALLBACK, AZ_EVAL_HASH, AZ_EVAL_NET, AZ_EVAL_RANDOM, AZ_EVAL_UNIFORM, EVAL_FN, AZ_PREC_BF16, AZ_PREC_BF16X3, AZ_PREC_F16X3, AZ_PREC_F32, AZ_PREC_FP16, AzError,
-                   ARENA_SINK, ArenaCfg, ArenaSummary, GAME_SINK, PROGRESS_FN, MoveRec as _lib_MoveRec, NetDesc, SearchCfg, SelfPlayCfg, check, lib)
+                   ARENA_SINK, ArenaCfg, ArenaSummary, ReplayCfg, GAME_SINK, PROGRESS_FN, MoveRec as _lib_MoveRec, NetDesc, SearchCfg, SelfPlayCfg, check, lib)
 
 __all__ = ["Engine", "HipNeuralNetwork", "ParallelMCTS", "SelfPlayManager", "Arena", "ArenaGameRecord", "EloRating", "GameRecord", "MoveData", "AzError",
-           "Dataset", "TrainingExample", "GAME_GOMOKU", "GAME_GO",
+           "Dataset", "TrainingExample", "GAME_GOMOKU", "GAME_GO", "ReplayBuffer", "replay_sym_cell", "replay_sample_plan",
            "AZ_PREC_F32", "AZ_PREC_BF16X3", "AZ_PREC_F16X3", "AZ_PREC_BF16", "AZ_PREC_FP16", "AZ_EVAL_NET", "AZ_EVAL_HASH", "AZ_EVAL_RANDOM", "AZ_EVAL_UNIFORM", "AZ_EVAL_CALLBACK",
            "gomoku_net_desc"]
 
@@ -541,6 +544,12 @@ class ParallelMCTS:
                                              int(r.thinking_time_ms), r.child_actions[:k])))
         return out
 
+    def attachReplay(self, rb):
+        """az_search_attach_replay: selfplayStep / az_selfplay_run stage every position they move from into
+        `rb` and commit finished games; None detaches.  Staged positions are discarded either way."""
+        check(lib().az_search_attach_replay(self.h, rb.h if rb is not None else None))
+        self._replay = rb      # kept alive with the handle
+
     def close(self):
         if self.h:
             if not getattr(self, "_borrowed", False):
@@ -946,6 +955,120 @@ class Dataset:
     def close(self):
         if self.h:
             lib().az_dataset_destroy(self.h)
+            self.h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+# ---------------------------------------------------------------------------- ReplayBuffer
+def replay_sym_cell(board_size, sym, cell):
+    """az_replay_sym_cell: the cell `cell` maps to under symmetry `sym` (0 identity; the enumeration is in
+    include/az_engine.h)."""
+    c = lib().az_replay_sym_cell(int(board_size), int(sym), int(cell))
+    if c < 0:
+        raise ValueError(f"replay_sym_cell({board_size}, {sym}, {cell}): argument out of range")
+    return c
+
+
+def replay_sample_plan(seed, call, n, committed, augment=True):
+    """az_replay_sample_plan: (idx int64 [n], sym int32 [n]) of sampling call `call` under `seed`."""
+    idx = np.zeros(max(n, 1), np.int64)
+    sym = np.zeros(max(n, 1), np.int32)
+    check(lib().az_replay_sample_plan(int(seed), int(call), int(n), int(committed), int(bool(augment)),
+                                      idx.ctypes.data_as(ctypes.POINTER(ctypes.c_int64)), _ip(sym)))
+    return idx[:n], sym[:n]
+
+
+class ReplayBuffer:
+    """A device-resident ring of training positions (az_replay_*): board record, visit counts by action, root
+    value and outcome.  Attach it to a ParallelMCTS (attachReplay); selfplayStep / generateGames fill it."""
+
+    def __init__(self, engine, game=GAME_GOMOKU, board_size=15, capacity=1 << 16, max_plies=None):
+        self.bs, self.game = board_size, game
+        self.A = board_size * board_size
+        self.NA = self.A + (1 if game == GAME_GO else 0)
+        self.C = 8 if game == GAME_GO else 11
+        if max_plies is None:
+            max_plies = 2 * self.A
+        cfg = ReplayCfg(game, board_size, capacity, max_plies)
+        h = ctypes.c_void_p()
+        check(lib().az_replay_create(engine.h, ctypes.byref(cfg), ctypes.byref(h)))
+        self.h, self.engine = h, engine
+
+    def info(self):
+        v = [ctypes.c_int64(0) for _ in range(5)]
+        check(lib().az_replay_info(self.h, *[ctypes.byref(x) for x in v]))
+        return dict(zip(("committed", "total_committed", "games", "dropped", "skipped"), (int(x.value) for x in v)))
+
+    def seed(self, seed):
+        """The seed of sample / sample_into; the call counter restarts at 0."""
+        check(lib().az_replay_seed(self.h, int(seed)))
+
+    def _outs(self, n):
+        m = max(n, 1)
+        return (np.zeros((m, self.C, self.bs, self.bs), np.float32), np.zeros((m, self.NA), np.float32),
+                np.zeros(m, np.float32), np.zeros(m, np.float32))
+
+    def gather(self, idx, sym=None):
+        """Ring slots idx under symmetries sym (None: identity): dict of states [n][C][bs][bs], policy [n][NA],
+        z, q, game_id, ply."""
+        idx = np.ascontiguousarray(idx, np.int64).reshape(-1)
+        n = idx.size
+        st, po, z, q = self._outs(n)
+        gid, ply = np.zeros(max(n, 1), np.int32), np.zeros(max(n, 1), np.int32)
+        sp = None
+        if sym is not None:
+            sym = np.ascontiguousarray(sym, np.int32).reshape(-1)
+            if sym.size != n:
+                raise ValueError("sym and idx differ in length")
+            sp = _ip(sym)
+        check(lib().az_replay_gather(self.h, idx.ctypes.data_as(ctypes.POINTER(ctypes.c_int64)), sp, n, _fp(st), _fp(po),
+                                     _fp(z), _fp(q), _ip(gid), _ip(ply)))
+        return dict(states=st[:n], policy=po[:n], z=z[:n], q=q[:n], game_id=gid[:n], ply=ply[:n])
+
+    def sample(self, n, augment=True):
+        """One sampling call to host arrays: dict of states, policy, z, q and the plan's idx, sym."""
+        st, po, z, q = self._outs(n)
+        idx, sym = np.zeros(max(n, 1), np.int64), np.zeros(max(n, 1), np.int32)
+        check(lib().az_replay_sample(self.h, n, int(bool(augment)), _fp(st), _fp(po), _fp(z), _fp(q),
+                                     idx.ctypes.data_as(ctypes.POINTER(ctypes.c_int64)), _ip(sym)))
+        return dict(states=st[:n], policy=po[:n], z=z[:n], q=q[:n], idx=idx[:n], sym=sym[:n])
+
+    def sample_into(self, states, policy, z=None, q=None, augment=True):
+        """One sampling call straight into contiguous float32 torch tensors on the engine's device: states
+        [n][C][bs][bs], policy [n][NA], optional z [n], q [n].  Returns when the tensors are written."""
+        n = int(states.shape[0])
+        want = {"states": (states, (n, self.C, self.bs, self.bs)), "policy": (policy, (n, self.NA)), "z": (z, (n,)),
+                "q": (q, (n,))}
+        ptr = {}
+        for name, (t, shape) in want.items():
+            if t is None:
+                ptr[name] = None
+                continue
+            if tuple(t.shape) != shape or not t.is_contiguous() or str(t.dtype) != "torch.float32" or not t.is_cuda:
+                raise ValueError(f"{name}: need a contiguous float32 device tensor of shape {shape}")
+            ptr[name] = ctypes.c_void_p(t.data_ptr())
+        check(lib().az_replay_sample_device(self.h, n, int(bool(augment)), ptr["states"], ptr["policy"], ptr["z"],
+                                            ptr["q"]))
+
+    def counts(self, idx):
+        """The raw visit counts by action of ring slots idx: (counts int32 [n][NA], sum int32 [n])."""
+        idx = np.ascontiguousarray(idx, np.int64).reshape(-1)
+        n = idx.size
+        c, s = np.zeros((max(n, 1), self.NA), np.int32), np.zeros(max(n, 1), np.int32)
+        check(lib().az_replay_counts(self.h, idx.ctypes.data_as(ctypes.POINTER(ctypes.c_int64)), n, _ip(c), _ip(s)))
+        return c[:n], s[:n]
+
+    def clear(self):
+        check(lib().az_replay_clear(self.h))
+
+    def close(self):
+        if self.h:
+            lib().az_replay_destroy(self.h)
             self.h = None
 
     def __del__(self):

@@ -63,6 +63,10 @@ class MoveRec(ctypes.Structure):
                 ("child_actions", P(c_int)), ("thinking_time_ms", c_int64)]
 
 
+class ReplayCfg(ctypes.Structure):
+    _fields_ = [("game", c_int), ("board_size", c_int), ("capacity", c_int), ("max_plies", c_int)]
+
+
 class ArenaCfg(ctypes.Structure):
     _fields_ = [("swap_colors", c_int), ("temperature", c_float), ("sample_moves", c_int), ("noise_alpha", c_float),
                 ("noise_eps", c_float)]
@@ -172,6 +176,19 @@ EXPORTS = {
     "az_dataset_permute": (c_int, [vp, P(c_int64)]),
     "az_dataset_gather": (c_int, [vp, P(c_int64), c_int, P(c_float), P(c_float), P(c_int), P(c_float)]),
     "az_dataset_profile_read": (c_int, [vp, P(ctypes.c_double), P(ctypes.c_double)]),
+    "az_replay_create": (c_int, [vp, P(ReplayCfg), P(vp)]),
+    "az_replay_destroy": (None, [vp]),
+    "az_search_attach_replay": (c_int, [vp, vp]),
+    "az_replay_info": (c_int, [vp, P(c_int64), P(c_int64), P(c_int64), P(c_int64), P(c_int64)]),
+    "az_replay_seed": (c_int, [vp, c_uint64]),
+    "az_replay_sample_plan": (c_int, [c_uint64, c_uint64, c_int, c_int64, c_int, P(c_int64), P(c_int)]),
+    "az_replay_sym_cell": (c_int, [c_int, c_int, c_int]),
+    "az_replay_gather": (c_int, [vp, P(c_int64), P(c_int), c_int, P(c_float), P(c_float), P(c_float), P(c_float), P(c_int),
+                                 P(c_int)]),
+    "az_replay_sample": (c_int, [vp, c_int, c_int, P(c_float), P(c_float), P(c_float), P(c_float), P(c_int64), P(c_int)]),
+    "az_replay_sample_device": (c_int, [vp, c_int, c_int, vp, vp, vp, vp]),
+    "az_replay_counts": (c_int, [vp, P(c_int64), c_int, P(c_int), P(c_int)]),
+    "az_replay_clear": (c_int, [vp]),
     "az_dist_unique_id": (c_int, [P(ctypes.c_ubyte)]),
     "az_dist_init": (c_int, [vp, c_int, c_int, P(ctypes.c_ubyte), c_int, P(vp)]),
     "az_dist_destroy": (None, [vp]),

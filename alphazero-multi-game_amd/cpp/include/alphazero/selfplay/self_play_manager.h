@@ -16,6 +16,7 @@ namespace alphazero {
 namespace selfplay {
 
 class Distributed;
+class ReplayBuffer;
 
 // Contiguous global game ids of one rank of a per-GPU job (the first total % world ranks take one
 // more) and the noise seed that keeps every game's record independent of the rank count (seed +
@@ -74,6 +75,9 @@ class SelfPlayManager {
     void setLeafParallelism(int leaves) { leaves_ = leaves; }
     int getLeafParallelism() const { return leaves_; }
     void setMaxMoves(int n) { maxMoves_ = n; }
+    // generateGames fills `rb` (replay_buffer.h; same game type, board and device as the run, else generateGames
+    // throws): every finished or cut game commits its positions.  Not owned; nullptr: none.
+    void setReplayBuffer(ReplayBuffer* rb) { replay_ = rb; }
     void setSeeds(unsigned noiseSeed, int noiseSeedStride) { noiseSeed_ = noiseSeed; noiseStride_ = noiseSeedStride; }
     // Evaluation log (tests: a game replayed through the CPU oracle): every network evaluation of device
     // slot `slot` (the game id while the games fit the slots) -- post-softmax policy [NA], value, feature
@@ -109,6 +113,7 @@ class SelfPlayManager {
     EvalLog log_;
     int firstGame_ = 0;
     Distributed* dist_ = nullptr;
+    ReplayBuffer* replay_ = nullptr;
     JobStats job_;
 };
 

@@ -16,6 +16,7 @@
 #include "alphazero/nn/random_policy_network.h"
 #include "alphazero/selfplay/dataset.h"
 #include "alphazero/selfplay/game_record.h"
+#include "alphazero/selfplay/replay_buffer.h"
 #include "alphazero/selfplay/distributed.h"
 #include "alphazero/selfplay/run_metadata.h"
 #include "alphazero/selfplay/self_play_manager.h"
@@ -78,6 +79,26 @@ class PyNeuralNetwork : public nn::NeuralNetwork {
     void enableDebugMode(bool) override {}
     void printModelSummary() const override {}
 };
+
+// a ReplayBuffer::Batch as a dict of numpy arrays: states [n][C][bs][bs], policy [n][NA], z, q, idx, sym and, from
+// gather, game_id and ply
+static py::dict replayBatchDict(const selfplay::ReplayBuffer::Batch& b, bool ids) {
+    py::array_t<float> st({(py::ssize_t)b.n, (py::ssize_t)b.planes, (py::ssize_t)b.boardSize, (py::ssize_t)b.boardSize});
+    py::array_t<float> po({(py::ssize_t)b.n, (py::ssize_t)b.policySize});
+    std::copy(b.states.begin(), b.states.end(), st.mutable_data());
+    std::copy(b.policy.begin(), b.policy.end(), po.mutable_data());
+    py::dict d;
+    d["states"] = st; d["policy"] = po;
+    d["z"] = py::array_t<float>((py::ssize_t)b.z.size(), b.z.data());
+    d["q"] = py::array_t<float>((py::ssize_t)b.q.size(), b.q.data());
+    d["idx"] = py::array_t<int64_t>((py::ssize_t)b.idx.size(), b.idx.data());
+    d["sym"] = py::array_t<int>((py::ssize_t)b.sym.size(), b.sym.data());
+    if (ids) {
+        d["game_id"] = py::array_t<int>((py::ssize_t)b.gameId.size(), b.gameId.data());
+        d["ply"] = py::array_t<int>((py::ssize_t)b.ply.size(), b.ply.data());
+    }
+    return d;
+}
 
 PYBIND11_MODULE(_alphazero_cpp, m) {
     m.doc() = "AlphaZero multi-game engine, MI355X (HIP) backend";
@@ -453,6 +474,42 @@ PYBIND11_MODULE(_alphazero_cpp, m) {
         .def("getExamples", &selfplay::Dataset::getExamples)
         .def("lastExtractMs", &selfplay::Dataset::lastExtractMs);
 
+    // engine extension: the device replay buffer (az_replay_*); arrays come back as numpy
+    py::class_<selfplay::ReplayBuffer>(m, "ReplayBuffer")
+        .def(py::init<core::GameType, int, int, int, int>(), py::arg("gameType"), py::arg("boardSize"), py::arg("capacity"),
+             py::arg("maxPlies"), py::arg("device") = -1)
+        .def("info", [](const selfplay::ReplayBuffer& self) {
+            const auto i = self.info();
+            py::dict d;
+            d["committed"] = i.committed; d["total_committed"] = i.totalCommitted; d["games"] = i.games;
+            d["dropped"] = i.dropped; d["skipped"] = i.skipped;
+            return d;
+        })
+        .def("seed", &selfplay::ReplayBuffer::seed)
+        .def("sample", [](selfplay::ReplayBuffer& self, int n, bool augment) {
+            return replayBatchDict(self.sample(n, augment), false);
+        }, py::arg("n"), py::arg("augment") = true)
+        .def("gather", [](const selfplay::ReplayBuffer& self, const std::vector<int64_t>& idx, const std::vector<int>& sym) {
+            return replayBatchDict(self.gather(idx, sym), true);
+        }, py::arg("idx"), py::arg("sym") = std::vector<int>{})
+        .def("sampleInto", [](selfplay::ReplayBuffer& self, int n, bool augment, uintptr_t st, uintptr_t po, uintptr_t z,
+                              uintptr_t q) {
+            // device addresses (torch tensors' data_ptr()); 0 for an output that is not wanted
+            self.sampleInto(n, augment, reinterpret_cast<float*>(st), reinterpret_cast<float*>(po),
+                            reinterpret_cast<float*>(z), reinterpret_cast<float*>(q));
+        }, py::arg("n"), py::arg("augment"), py::arg("states"), py::arg("policy"), py::arg("z") = 0, py::arg("q") = 0)
+        .def("counts", [](const selfplay::ReplayBuffer& self, const std::vector<int64_t>& idx) {
+            std::vector<int> sum;
+            const std::vector<int> c = self.counts(idx, &sum);
+            py::array_t<int> a({(py::ssize_t)idx.size(), (py::ssize_t)self.policySize()});
+            std::copy(c.begin(), c.end(), a.mutable_data());
+            return py::make_tuple(a, py::array_t<int>((py::ssize_t)sum.size(), sum.data()));
+        })
+        .def("clear", &selfplay::ReplayBuffer::clear)
+        .def_static("symCell", &selfplay::ReplayBuffer::symCell)
+        .def_static("samplePlan", &selfplay::ReplayBuffer::samplePlan, py::arg("seed"), py::arg("call"), py::arg("n"),
+                    py::arg("committed"), py::arg("augment") = true);
+
     py::class_<selfplay::RunMetadata>(m, "RunMetadata")
         .def(py::init<>())
         .def_readwrite("game", &selfplay::RunMetadata::game)
@@ -591,6 +648,8 @@ PYBIND11_MODULE(_alphazero_cpp, m) {
         .def("setLeafParallelism", &selfplay::SelfPlayManager::setLeafParallelism, py::arg("leaves"))
         .def("getLeafParallelism", &selfplay::SelfPlayManager::getLeafParallelism)
         .def("setMaxMoves", &selfplay::SelfPlayManager::setMaxMoves)
+        .def("setReplayBuffer", &selfplay::SelfPlayManager::setReplayBuffer, py::arg("replayBuffer").none(true),
+             py::keep_alive<1, 2>())
         .def("setSeeds", &selfplay::SelfPlayManager::setSeeds)
         .def("setShard", &selfplay::SelfPlayManager::setShard)
         .def("getFirstGameId", &selfplay::SelfPlayManager::getFirstGameId)

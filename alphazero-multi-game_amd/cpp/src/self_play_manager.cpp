@@ -12,6 +12,7 @@
 #include "alphazero/games/gomoku/gomoku_state.h"
 #include "alphazero/nn/hip_neural_network.h"
 #include "alphazero/selfplay/distributed.h"
+#include "alphazero/selfplay/replay_buffer.h"
 
 namespace alphazero {
 namespace selfplay {
@@ -148,6 +149,10 @@ int SelfPlayManager::runGames(core::GameType type, int bs, bool variant, std::ve
     // variant rules: createGameState(GOMOKU, bs, true) is Renju (igamestate.cpp:24-27)
     mcts::applyGomokuRules(s, az_gomoku_rules{variant ? 1 : 0, 0, 0});
     if (leaves_ != 1 && az_search_set_leaves(s, leaves_)) {
+        az_search_destroy(s);
+        throw std::runtime_error(az_last_error());
+    }
+    if (replay_ && az_search_attach_replay(s, replay_->handle())) {
         az_search_destroy(s);
         throw std::runtime_error(az_last_error());
     }

@@ -10,6 +10,7 @@
 #include "tree.h"
 
 struct az_net;
+struct az_replay;
 
 struct az_search {
     az_engine* e = nullptr;
@@ -71,6 +72,10 @@ struct az_search {
     std::vector<int> sp_slots;
     std::vector<az_move_rec> sp_moves;
     int sp_next_id = 0;             // one past the highest game id started on the handle (az_selfplay_step restarts)
+    std::vector<int> slot_id;       // the game id each slot plays (search_new_games' seed id; default the slot index)
+    // az_search_attach_replay: the self-play driver stages every root it moves from and commits finished games
+    // (replay.hip); null: the driver launches nothing more than it does without the feature
+    az_replay* replay = nullptr;
     // device-resident copies of the TreeDev variants the per-step kernels take (tree_dev()): those
     // kernels get one 8-byte pointer instead of the ~550-byte struct by value, on ~38k dispatches per
     // C3 move.  Slot i's host shadow (pinned, the source of its async upload) is h_tree.p[i].
@@ -116,3 +121,11 @@ int search_apply_dev(az_search* s, int* terminal, int* result);
 void prefetch_noise(az_search* s, float alpha, const std::vector<uint8_t>& want);
 // the prefetch job done (every accessor of s->rng / s->pf calls this first)
 void pf_wait(az_search* s);
+// The replay buffer's hooks (replay.hip), for a handle with s->replay set; the caller holds s->mu.
+// stage: after search_select and before search_apply_dev, one position per playing game that moves.
+int replay_stage(az_search* s);
+// commit the staged positions of the finished slots (ascending) with their GameResults (0: cut), in one launch
+int replay_commit(az_search* s, const std::vector<int>& slots, const std::vector<int>& results);
+// empty the staging of the listed slots (null: every slot) and refresh the slots' game ids
+int replay_discard(az_search* s, const int* games, int n);
+void replay_detach(az_search* s);

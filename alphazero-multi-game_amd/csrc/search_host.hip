@@ -462,10 +462,12 @@ int search_new_games(az_search* s, const int* games, int n, const int* seed_ids)
         s->hist[g].clear();
         s->roots_ready = false;                          // a fresh root: unexpanded
         const int id = seed_ids ? seed_ids[i] : g;
+        s->slot_id[g] = id;
         s->sp_next_id = std::max(s->sp_next_id, id + 1);
         pf_drop(s, g);
         s->rng[g].seed(s->c.noise_seed + (uint32_t)(s->c.noise_seed_stride * id));
     }
+    if (s->replay) return replay_discard(s, games, n);   // a new game in the slot: its staged positions go
     return 0;
 }
 
@@ -784,6 +786,8 @@ int search_create(az_engine* e, az_net* net, const az_search_cfg* c, int net_bat
     s->stones.assign(G, 0); s->active.assign(G, 0); s->fresh.assign(G, 1); s->ply.assign(G, 0); s->expanded.assign(G, 0);
     s->rng.resize(G);
     s->hist.assign(G, {});
+    s->slot_id.resize(G);
+    for (int g = 0; g < G; ++g) s->slot_id[g] = g;
     if (!s->h_noise.get((size_t)G * NA)) return az_fail(AZ_ERR_OOM, "hipHostMalloc (noise)");
     std::fill(s->h_noise.p, s->h_noise.p + (size_t)G * NA, 0.0f);
     s->h_mask.assign(G, 0);
@@ -797,6 +801,10 @@ void az_search_destroy(az_search* s) {
     if (!s) return;
     pf_wait(s);
     (void)hipSetDevice(s->e->device);
+    {
+        std::lock_guard<std::mutex> lk(s->mu);
+        replay_detach(s);
+    }
     delete s;   // its pool frees every device buffer
 }
 

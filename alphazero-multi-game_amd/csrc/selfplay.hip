@@ -45,10 +45,18 @@ int az_selfplay_step(az_search* s, const az_selfplay_cfg* cfg, int64_t* moves_do
     STEP_TRACE("select");
     if (int r = search_select(s, 1, temps.data(), 0.0f, actions.data(), vals, probs, cact, nch))
         return r;
+    if (s->replay)
+        if (int r = replay_stage(s)) return r;
     STEP_TRACE("apply");
     const int64_t ms = std::chrono::duration_cast<std::chrono::milliseconds>(std::chrono::steady_clock::now() - t0).count();
     std::vector<int> term(G), res(G);
     if (int r = search_apply_dev(s, term.data(), res.data())) return r;
+    if (s->replay) {   // the games this move ended, in slot order
+        std::vector<int> fin, fres;
+        for (int g = 0; g < G; ++g)
+            if (was_active[g] && !s->active[g]) { fin.push_back(g); fres.push_back(res[g]); }
+        if (int r = replay_commit(s, fin, fres)) return r;
+    }
     int64_t moves = 0;
     std::vector<uint8_t> noise_mask(G, 0);
     const int none = s->t.game == GAME_GO ? AZ_ACTION_NONE : -1;
@@ -138,6 +146,8 @@ int az_selfplay_run(az_search* s, const az_selfplay_cfg* cfg, int total_games, i
         if (int r = search_new_games(s, slots.data(), (int)slots.size(), ids.data())) return r;
         return search_noise(s, s->c.dirichlet_alpha, s->c.dirichlet_eps, mask.data());   // :184
     };
+    if (s->replay)   // positions staged by earlier calls belong to games this run abandons
+        if (int r = replay_discard(s, nullptr, 0)) return r;
     std::vector<int> first;
     for (int g = 0; g < G && g < total_games; ++g) first.push_back(g);
     if (int r = start(first)) return r;
@@ -155,6 +165,8 @@ int az_selfplay_run(az_search* s, const az_selfplay_cfg* cfg, int total_games, i
             return r;
         const int64_t ms = std::chrono::duration_cast<std::chrono::milliseconds>(std::chrono::steady_clock::now() - t0).count();
         std::vector<int> was_active = s->active, ply0 = s->ply;
+        if (s->replay)
+            if (int r = replay_stage(s)) return r;
         for (int g = 0; g < G; ++g) {
             if (!was_active[g] || actions[g] == none) continue;
             Rec& R = rec[g];
@@ -177,6 +189,11 @@ int az_selfplay_run(az_search* s, const az_selfplay_cfg* cfg, int total_games, i
             done.push_back(g);
         }
         if (int r = search_noise(s, s->c.dirichlet_alpha, s->c.dirichlet_eps, noise.data())) return r;
+        if (s->replay) {   // finished or cut (z = 0) games, in slot order, before their slots restart
+            std::vector<int> dres;
+            for (int g : done) dres.push_back(s->active[g] ? 0 : res[g]);
+            if (int r = replay_commit(s, done, dres)) return r;
+        }
         for (int g : done) {
             Rec& R = rec[g];
             for (size_t i = 0; i < R.moves.size(); ++i) { R.moves[i].policy = R.pol[i].data(); R.moves[i].child_actions = R.cact[i].data(); }
@@ -198,6 +215,8 @@ int az_selfplay_run(az_search* s, const az_selfplay_cfg* cfg, int total_games, i
         }
     }
     pf_wait(s);
+    if (s->replay)   // an abort leaves games unfinished: their staged positions go
+        if (int r = replay_discard(s, nullptr, 0)) return r;
     HIPCHK(hipStreamSynchronize(st));
     return 0;
 }

@@ -121,6 +121,39 @@ static_assert(offsetof(TreeDev, sel) == offsetof(TreeDev, log_n) + sizeof(int*),
 static_assert(offsetof(TreeDev, stamp_game) == offsetof(TreeDev, wid_tab) + sizeof(int*), "TreeDev hole after wid_tab");
 static_assert(offsetof(TreeDev, tt_mask) == 10 * sizeof(int), "TreeDev hole before tt_mask");
 
+// Replay buffer (az_replay_*, replay.hip): action-space training targets kept on the device.  A position is
+// a record of `rec` bytes -- board [A] u8, Go: min(10, liberties) [A] u8, then at `moff` (4-aligned) eight
+// int32 {side to move, ko point, last six moves}: the inputs of az_leaf_planes_v -- a counts row int32 [NA]
+// (visit counts by action, Go's pass at A) and one int32 / fp32 per column below.  Staged rows: slot g's
+// position p at g * max_plies + p; ring rows: [capacity].
+enum { RP_HEAD = 0, RP_GAMES = 1, RP_DROPPED = 2, RP_SKIPPED = 3, RP_DONE = 4, RP_NCTR = 8 };
+struct ReplayRows {
+    uint8_t* rec; int* cnt; int* sum; float* q; int* gid; int* ply; int* player;
+    float* z;                    // ring only
+};
+struct ReplayDev {
+    int game, bs, A, NA, C;
+    int rec, moff;               // record bytes (a multiple of 16), offset of its meta ints
+    int capacity, max_plies;
+    int pad = 0;
+    ReplayRows st, ring;
+    int* st_n;                   // [G] positions staged for the slot's game (counts past max_plies: dropped)
+    int* slot_gid;               // [G] the game id each slot plays
+    long long* ctr;              // [RP_NCTR]: ring head = positions ever committed, games, dropped, skipped, RP_DONE:
+                                 // the blocks of the running k_replay_commit that have finished
+};
+// sym = k + 4 f: if f the columns are mirrored, (r, c) -> (r, n - c); then k quarter turns (r, c) -> (c, n - r)
+#if defined(__HIPCC__)
+__host__ __device__
+#endif
+inline int replay_sym_cell(int bs, int sym, int cell) {
+    const int n = bs - 1;
+    int r = cell / bs, c = cell % bs;
+    if (sym & 4) c = n - c;
+    for (int k = sym & 3; k > 0; --k) { const int t = r; r = c; c = n - t; }
+    return r * bs + c;
+}
+
 // Training-example extraction (Dataset::extractExamples + augmentExample).
 // Records are flattened: game g owns moves [move_off[g], move_off[g+1]); move m owns policy
 // floats [pol_off[m], pol_off[m] + n_children[m]).  Pre-shuffle example e = m * K + s (s = 0

@@ -35,7 +35,17 @@ __global__ void k_tt_clear(TreeDev t, const int* games, int n);
 __global__ void k_root_nchild(TreeDev t, int* out);
 __global__ void k_root_children(TreeDev t, int g, int* act, int* N, int* VL, float* W, float* P, int* n, int* rootinfo,
                                 float* rootW);
-// replay dataset (dataset.hip)
+// replay buffer (replay.hip).  stage: one wave per game slot -- the root position and its children's visit counts of
+// every playing game whose actions[g] is a move, into the slot's staging rows.  commit: one block per finished slot
+// slots[i] (ascending), GameResult results[i]: its staged rows into the ring after those of the slots before it.
+// gather: one block per sample -- ring row idx[i] under symmetry sym[i] (null: 0) as planes, policy, z, q, game id, ply
+// (the last four optional).  counts: the raw counts rows.
+void az_launch_replay_stage(const TreeDev& t, const ReplayDev& r, const int* actions, const float* values, hipStream_t st);
+void az_launch_replay_commit(const ReplayDev& r, const int* slots, const int* results, int n, hipStream_t st);
+void az_launch_replay_gather(const ReplayDev& r, const long long* idx, const int* sym, int n, float* states, float* policy,
+                             float* z, float* q, int* gid, int* ply, hipStream_t st);
+void az_launch_replay_counts(const ReplayDev& r, const long long* idx, int n, int* counts, int* sum, hipStream_t st);
+// training-example dataset (dataset.hip)
 __global__ void k_dataset_extract(DatasetDev d, TreeDev t);
 __global__ void k_dataset_gather(const float* states, const float* policy, const int* plen, const float* value, int row,
                                  int NA, const long long* idx, int n, float* ostates, float* opolicy, int* oplen,

@@ -2269,3 +2269,199 @@ __global__ __launch_bounds__(256) void k_dataset_gather(const float* states, con
     for (int k = threadIdx.x; k < NA; k += 256) opolicy[(long long)i * NA + k] = policy[j * NA + k];
     if (threadIdx.x == 0) { oplen[i] = plen[j]; ovalue[i] = value[j]; }
 }
+
+// ---------------------------------------------------------------------------
+// Replay buffer (az_replay_*, replay.hip; layout: ReplayDev in tree.h).
+//
+// K-R1: one wave per game slot, between k_select_action and k_apply: the root children's visit counts scattered to
+// action index (clamped at 0: progressive widening leaves negative N) and the root's position record -- what
+// write_leafrec / go_write_leafrec store for a leaf, here for the root -- into the slot's next staging row.
+__global__ __launch_bounds__(64) void k_replay_stage(TreeDev t, ReplayDev r, const int* actions, const float* values) {
+    const int g = blockIdx.x;
+    const int lane = threadIdx.x;
+    __shared__ uint8_t board[AZ_MAXA];
+    __shared__ int cnt[AZ_MAXNA];
+    __shared__ GoLds gl;
+    if (g >= t.G) return;
+    const bool go = t.game == GAME_GO;
+    if (!t.active[g] || actions[g] == (go ? -2 : -1)) return;     // no move: nothing staged
+    const int A = t.A, NA = t.NA;
+    GamePtrs nd = game_nodes(t.nd, (size_t)g * t.ncap);
+    const int root = t.rnode[g];
+    const int fc = nd.first[root], nc = min((int)nd.cnt[root], NA);
+    for (int k = lane; k < NA; k += 64) cnt[k] = 0;
+    __syncthreads();
+    int sum = 0;
+    for (int i = lane; i < nc; i += 64) {
+        const int a = nd.act[fc + i];
+        const int v = max(0, nd.N[fc + i]);
+        const int k = a < 0 ? A : a;                               // Go's pass (-1) sits at A
+        if (k < NA) { cnt[k] = v; sum += v; }
+    }
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) sum += __shfl_xor(sum, o);
+    if (sum <= 0) {
+        if (lane == 0) atomicAdd(reinterpret_cast<unsigned long long*>(r.ctr + RP_SKIPPED), 1ULL);
+        return;
+    }
+    const int n = r.st_n[g];
+    if (n >= r.max_plies) {
+        if (lane == 0) atomicAdd(reinterpret_cast<unsigned long long*>(r.ctr + RP_DROPPED), 1ULL);
+        return;
+    }
+    const uint8_t* rb = t.rboard + (size_t)g * A;
+    for (int a = lane; a < A; a += 64) board[a] = rb[a];
+    __syncthreads();
+    const size_t row = (size_t)g * r.max_plies + n;
+    uint8_t* rec = r.st.rec + row * r.rec;
+    if (go) {
+        go_groups(t, board, gl, lane, 64);
+        for (int a = lane; a < A; a += 64) {
+            rec[a] = board[a];
+            rec[A + a] = board[a] ? (uint8_t)min(10, (int)gl.glib[gl.gid[a]]) : 0;
+        }
+    } else {
+        for (int a = lane; a < A; a += 64) rec[a] = board[a];
+    }
+    int* meta = reinterpret_cast<int*>(rec + r.moff);
+    const int player = t.rplayer[g];
+    if (lane == 0) meta[0] = player;
+    if (lane == 1) meta[1] = go ? t.rko[g] : -1;
+    if (lane < 6) meta[2 + lane] = go ? -1 : t.rhist[g * 6 + lane];
+    int* crow = r.st.cnt + row * NA;
+    for (int k = lane; k < NA; k += 64) crow[k] = cnt[k];
+    if (lane == 0) {
+        r.st.sum[row] = sum; r.st.q[row] = values[g]; r.st.gid[row] = r.slot_gid[g]; r.st.ply[row] = t.rply[g];
+        r.st.player[row] = player;
+        r.st_n[g] = n + 1;
+    }
+}
+
+// K-R2: one block per finished slot (slots ascending): its staged rows go to the ring behind those of the slots before
+// it, position k of the commit order at ring row k % capacity, with z for the side to move.  Rows that the same
+// commit would overwrite again (more than `capacity` positions at once) are not written.  The last block to finish
+// moves the head and empties the slots' staging.
+__global__ __launch_bounds__(256) void k_replay_commit(ReplayDev r, const int* slots, const int* results, int n) {
+    const int i = blockIdx.x;
+    const int tid = threadIdx.x;
+    __shared__ unsigned long long s_before, s_total;
+    if (i >= n) return;
+    if (tid == 0) { s_before = 0; s_total = 0; }
+    __syncthreads();
+    unsigned long long before = 0, total = 0;
+    for (int j = tid; j < n; j += 256) {
+        const unsigned long long c = (unsigned long long)r.st_n[slots[j]];
+        if (j < i) before += c;
+        total += c;
+    }
+    if (before) atomicAdd(&s_before, before);
+    if (total) atomicAdd(&s_total, total);
+    __syncthreads();
+    const long long head = r.ctr[RP_HEAD];
+    const long long base = head + (long long)s_before, end = head + (long long)s_total;
+    const int g = slots[i];
+    const int cnt = r.st_n[g];
+    const int res = results[i];
+    const int NA = r.NA, rec16 = r.rec / 16;
+    for (int p = 0; p < cnt; ++p) {
+        const long long k = base + p;
+        if (k < end - r.capacity) continue;
+        const size_t src = (size_t)g * r.max_plies + p, dst = (size_t)(k % r.capacity);
+        const uint4* s4 = reinterpret_cast<const uint4*>(r.st.rec + src * r.rec);
+        uint4* d4 = reinterpret_cast<uint4*>(r.ring.rec + dst * r.rec);
+        for (int x = tid; x < rec16; x += 256) d4[x] = s4[x];
+        for (int x = tid; x < NA; x += 256) r.ring.cnt[dst * NA + x] = r.st.cnt[src * NA + x];
+        if (tid == 0) {
+            const int player = r.st.player[src];
+            const float gv = res == R_WIN1 ? 1.0f : res == R_WIN2 ? -1.0f : 0.0f;
+            r.ring.z[dst] = gv == 0.0f ? 0.0f : (player == 2 ? -gv : gv);
+            r.ring.sum[dst] = r.st.sum[src]; r.ring.q[dst] = r.st.q[src]; r.ring.gid[dst] = r.st.gid[src];
+            r.ring.ply[dst] = r.st.ply[src]; r.ring.player[dst] = player;
+        }
+    }
+    __syncthreads();
+    if (tid == 0) {
+        __threadfence();
+        const unsigned long long done = atomicAdd(reinterpret_cast<unsigned long long*>(r.ctr + RP_DONE), 1ULL);
+        if (done == (unsigned long long)(n - 1)) {     // every block has read the staged counts and the head
+            for (int j = 0; j < n; ++j) r.st_n[slots[j]] = 0;
+            r.ctr[RP_HEAD] = end;
+            r.ctr[RP_GAMES] += n;
+            r.ctr[RP_DONE] = 0;
+        }
+    }
+}
+
+// K-R3: one block per sample.  The record of ring row idx[i] is mapped by symmetry sym[i] into LDS -- every cell with
+// its liberties, the last moves and the ko point -- and az_leaf_planes_v builds the planes of the MAPPED position, so
+// the coordinate planes are what the net sees in play; the policy count / sum is permuted by the same cell map (the
+// pass stays).  Plane and policy stores are contiguous over the threads.
+__global__ __launch_bounds__(256) void k_replay_gather(ReplayDev r, const long long* idx, const int* sym, int n,
+                                                       float* states, float* policy, float* z, float* q, int* gid,
+                                                       int* ply) {
+#pragma clang fp contract(off)
+    const int i = blockIdx.x;
+    const int tid = threadIdx.x;
+    __shared__ uint8_t mb[AZ_MAXA], ml[AZ_MAXA];
+    __shared__ int meta[8];
+    __shared__ float pol[AZ_MAXNA];
+    if (i >= n) return;
+    const long long j = idx[i];
+    const int s = sym ? sym[i] : 0;
+    const int A = r.A, NA = r.NA, bs = r.bs, C = r.C;
+    const int go = r.game == GAME_GO;
+    const uint8_t* rec = r.ring.rec + (size_t)j * r.rec;
+    const int* cnt = r.ring.cnt + (size_t)j * NA;
+    const float fsum = (float)r.ring.sum[j];
+    for (int a = tid; a < A; a += 256) {
+        const int d = replay_sym_cell(bs, s, a);
+        mb[d] = rec[a];
+        ml[d] = go ? rec[A + a] : (uint8_t)0;
+        pol[d] = (float)cnt[a] / fsum;
+    }
+    if (tid == 0 && NA > A) pol[A] = (float)cnt[A] / fsum;
+    if (tid < 8) {
+        int v = reinterpret_cast<const int*>(rec + r.moff)[tid];
+        if (tid >= 1 && v >= 0 && v < A) v = replay_sym_cell(bs, s, v);
+        meta[tid] = v;
+    }
+    __syncthreads();
+    float* o = states + (size_t)i * C * A;
+    for (int a = tid; a < A; a += 256) {
+        float c[16];
+        az_leaf_planes_v(mb[a], ml[a], meta, go, bs, a, c);
+#pragma unroll
+        for (int k = 0; k < 16; ++k)
+            if (k < C) o[(size_t)k * A + a] = c[k];
+    }
+    for (int k = tid; k < NA; k += 256) policy[(size_t)i * NA + k] = pol[k];
+    if (tid == 0) {
+        if (z) z[i] = r.ring.z[j];
+        if (q) q[i] = r.ring.q[j];
+        if (gid) gid[i] = r.ring.gid[j];
+        if (ply) ply[i] = r.ring.ply[j];
+    }
+}
+
+// The raw counts rows of ring rows idx[0..n) (tests, diagnostics).
+__global__ __launch_bounds__(256) void k_replay_counts(ReplayDev r, const long long* idx, int n, int* counts, int* sum) {
+    const int i = blockIdx.x;
+    if (i >= n) return;
+    const long long j = idx[i];
+    for (int k = threadIdx.x; k < r.NA; k += 256) counts[(size_t)i * r.NA + k] = r.ring.cnt[(size_t)j * r.NA + k];
+    if (threadIdx.x == 0 && sum) sum[i] = r.ring.sum[j];
+}
+
+void az_launch_replay_stage(const TreeDev& t, const ReplayDev& r, const int* actions, const float* values, hipStream_t st) {
+    hipLaunchKernelGGL(k_replay_stage, dim3(t.G), dim3(64), 0, st, t, r, actions, values);
+}
+void az_launch_replay_commit(const ReplayDev& r, const int* slots, const int* results, int n, hipStream_t st) {
+    hipLaunchKernelGGL(k_replay_commit, dim3(n), dim3(256), 0, st, r, slots, results, n);
+}
+void az_launch_replay_gather(const ReplayDev& r, const long long* idx, const int* sym, int n, float* states, float* policy,
+                             float* z, float* q, int* gid, int* ply, hipStream_t st) {
+    hipLaunchKernelGGL(k_replay_gather, dim3(n), dim3(256), 0, st, r, idx, sym, n, states, policy, z, q, gid, ply);
+}
+void az_launch_replay_counts(const ReplayDev& r, const long long* idx, int n, int* counts, int* sum, hipStream_t st) {
+    hipLaunchKernelGGL(k_replay_counts, dim3(n), dim3(256), 0, st, r, idx, n, counts, sum);
+}

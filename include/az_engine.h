@@ -561,6 +561,78 @@ int az_dataset_gather(az_dataset* d, const int64_t* idx, int n, float* states, f
  * extraction kernel. */
 int az_dataset_profile_read(az_dataset* d, double* extract_ms, double* bytes);
 
+/* ---------------------------------------------------------------- replay */
+/* A device-resident replay buffer that self-play fills and a trainer samples: action-space training
+ * targets (the Dataset above reproduces the reference's child-order examples; this one is what a policy
+ * head indexed by action trains on).  Opt-in: a search handle with no buffer attached launches exactly
+ * the kernels it launches without this section.
+ *
+ * Staging.  With a buffer attached, az_selfplay_step / az_selfplay_run stage one position per game that
+ * moves, between the action choice and the move: the root's position record (the inputs of the feature
+ * planes: board, side to move, last six moves -- Go: board, ko point, min(10, liberties) per cell), the
+ * visit counts of the root's children scattered to action index (int32 [NA]; Go's pass at bs*bs; each
+ * clamped at 0; a position whose clamped sum is 0 is not staged and counts as `skipped`), the root value
+ * (az_move_rec::value), game id, ply and side to move.  The counts do not depend on the temperature.
+ * Commit.  When a game finishes (terminal, or cut at max_moves in az_selfplay_run) its staged positions
+ * move into the ring in ply order with z for the side to move at each: +1 win, -1 loss, 0 for a draw or
+ * a cut game (Dataset::extractExamples, dataset.cpp:86-99).  Games finishing in one step commit in slot
+ * order.  The ring holds `capacity` positions and overwrites the oldest.  A slot stages at most
+ * max_plies positions of a game; later ones are dropped (`dropped`), the first max_plies still commit.
+ * az_search_new_games* on a slot, an abort of az_selfplay_run and detaching discard staged positions;
+ * positions of unfinished games are never visible.
+ * Gather.  Ring slot i under symmetry s: states fp32 [C][bs][bs] as az_net_forward takes them (11 planes
+ * Gomoku, 8 Go), policy fp32 [NA] = (float)count / (float)sum, z, q (the root value), game id, ply.
+ * The symmetry is applied to the RECORD -- cells, last moves and ko point are mapped, liberties travel
+ * with their cell -- and the standard plane builder runs on the mapped record: the sample is the planes
+ * of the game whose every move was mapped (the coordinate planes stay what the net sees in play).  The
+ * policy is permuted by the same cell map; the pass index is fixed.
+ * Symmetries (az_replay_sym_cell): cell = row * bs + col, n = bs - 1, sym = k + 4 f: if f, the columns
+ * are mirrored first, (r, c) -> (r, n - c); then k quarter turns (r, c) -> (c, n - r).
+ *   0 (r, c)       1 (c, n-r)     2 (n-r, n-c)   3 (n-c, r)
+ *   4 (r, n-c)     5 (n-c, n-r)   6 (n-r, c)     7 (c, r)
+ * Sampling = plan + gather.  The plan is a pure host function: Philox4x32-10 with key (seed lo, seed hi)
+ * and counter (i, call lo, call hi, 0) gives out0..3; idx[i] = (out0 * committed) >> 32,
+ * sym[i] = augment ? out1 & 7 : 0.  az_replay_sample uses the handle's seed and a call counter that
+ * starts at 0 (az_replay_seed resets it) and advances by one per sampling call. */
+typedef struct az_replay az_replay;
+typedef struct az_replay_cfg {
+    int game;             /* AZ_GAME_GOMOKU / AZ_GAME_GO */
+    int board_size;
+    int capacity;         /* ring positions, >= 1 */
+    int max_plies;        /* staged positions per game slot, >= 1 */
+} az_replay_cfg;
+int az_replay_create(az_engine* e, const az_replay_cfg* cfg, az_replay** out);
+/* Detaches from its search handle first.  Not to be called while another thread steps that handle. */
+void az_replay_destroy(az_replay* r);
+/* Attach r to s (null detaches).  AZ_ERR_ARG: game or board differ, or another engine; AZ_ERR_STATE: r is
+ * attached to another handle.  Every evaluator, search option, leaf parallelism and rule set is allowed:
+ * staging only reads roots.  Attaching and detaching discard staged positions. */
+int az_search_attach_replay(az_search* s, az_replay* r);
+/* committed = min(total_committed, capacity); games: finished games committed; any pointer may be null. */
+int az_replay_info(az_replay* r, int64_t* committed, int64_t* total_committed, int64_t* games, int64_t* dropped,
+                   int64_t* skipped);
+int az_replay_seed(az_replay* r, uint64_t seed);
+/* Host only.  1 <= committed < 2^32; idx and sym hold n entries. */
+int az_replay_sample_plan(uint64_t seed, uint64_t call, int n, int64_t committed, int augment, int64_t* idx, int* sym);
+/* Host only: the cell `cell` maps to under `sym` on a bs x bs board; -1 for arguments out of range. */
+int az_replay_sym_cell(int board_size, int sym, int cell);
+/* Ring slots idx[0..n) under sym[0..n) (null: identity) to host buffers: states [n][C][bs][bs], policy
+ * [n][NA], required; z, q, game_id, ply [n], optional.  AZ_ERR_ARG: an index outside [0, committed),
+ * a symmetry outside 0..7. */
+int az_replay_gather(az_replay* r, const int64_t* idx, const int* sym, int n, float* states, float* policy, float* z,
+                     float* q, int* game_id, int* ply);
+/* One plan (the handle's seed and call counter) and its gather; idx_out / sym_out (optional) receive the
+ * plan.  AZ_ERR_STATE on an empty buffer. */
+int az_replay_sample(az_replay* r, int n, int augment, float* states, float* policy, float* z, float* q,
+                     int64_t* idx_out, int* sym_out);
+/* The same into caller-supplied device memory on the handle's device (e.g. torch tensors' data_ptr()):
+ * d_states, d_policy required, d_z, d_q optional.  The engine stream is synchronised before returning. */
+int az_replay_sample_device(az_replay* r, int n, int augment, float* d_states, float* d_policy, float* d_z, float* d_q);
+/* The raw counts of ring slots idx[0..n): counts [n][NA] int32, sum [n] (optional). */
+int az_replay_counts(az_replay* r, const int64_t* idx, int n, int* counts, int* sum);
+/* Empty the ring and the counters; staged positions and the attachment stay. */
+int az_replay_clear(az_replay* r);
+
 /* ------------------------------------------------------------ multi-GPU */
 /* One process per GPU (the reference's per-GPU self_play processes,
  * python/scripts/orchestrate_selfplay.py:303-311,741-749), games sharded by contiguous global id
