@@ -27,7 +27,7 @@ from ._lib import (AZ_GO_RULES_SET, AZ_MAX_LEAVES, GomokuRules, AZ_SEL_PROGRESSI
 __all__ = ["Engine", "HipNeuralNetwork", "ParallelMCTS", "SelfPlayManager", "Arena", "ArenaGameRecord", "EloRating", "GameRecord", "MoveData", "AzError",
            "Dataset", "TrainingExample", "GAME_GOMOKU", "GAME_GO", "ReplayBuffer", "replay_sym_cell", "replay_sample_plan",
            "AZ_PREC_F32", "AZ_PREC_BF16X3", "AZ_PREC_F16X3", "AZ_PREC_BF16", "AZ_PREC_FP16", "AZ_EVAL_NET", "AZ_EVAL_HASH", "AZ_EVAL_RANDOM", "AZ_EVAL_UNIFORM", "AZ_EVAL_CALLBACK",
-           "gomoku_net_desc"]
+           "gomoku_net_desc", "state_dict_blob"]
 
 _f = ctypes.POINTER(ctypes.c_float)
 _i = ctypes.POINTER(ctypes.c_int)
@@ -72,6 +72,28 @@ def gomoku_net_desc(board_size=15, channels=256, blocks=20, precision=AZ_PREC_F3
     """Residual policy/value net of BASELINE.json (C2: 6x64, C3: 20x256) for Gomoku."""
     return NetDesc(board_size, in_planes, channels, blocks, board_size * board_size, head_channels, pool, fc_hidden,
                    residual, conv_bias, precision, max_batch)
+
+
+def state_dict_blob(state_dict, out=None):
+    """The canonical parameter blob of a torch module's state_dict: its entries flattened and concatenated in
+    order, num_batches_tracked skipped, as one float32 tensor on the entries' device (or written into `out`, a
+    contiguous float32 tensor of that many elements, which is returned).  HipNeuralNetwork.load_weights_device
+    takes the result as it is; load_weights takes blob.cpu().numpy().  The module's state_dict must be in
+    blob order (conv, BN weight / bias / running_mean / running_var, ... as az_net_num_params counts them)."""
+    import torch
+    parts = [v for k, v in state_dict.items() if not k.endswith("num_batches_tracked")]
+    total = sum(int(v.numel()) for v in parts)
+    if out is None:
+        out = torch.empty(total, dtype=torch.float32, device=parts[0].device if parts else "cpu")
+    elif out.dtype != torch.float32 or not out.is_contiguous() or out.numel() != total:
+        raise ValueError(f"out: need a contiguous float32 tensor of {total} elements")
+    flat, off = out.view(-1), 0
+    with torch.no_grad():
+        for v in parts:
+            n = int(v.numel())
+            flat[off:off + n].copy_(v.reshape(-1))
+            off += n
+    return out
 
 
 def randwire_net_desc(board_size=15, channels=128, blocks=20, in_planes=11, max_batch=256, action_size=None):
@@ -130,6 +152,18 @@ class HipNeuralNetwork:
     def load_weights(self, blob):
         blob = np.ascontiguousarray(blob, dtype=np.float32).reshape(-1)
         check(lib().az_net_load_weights(self.h, _fp(blob), blob.size))
+
+    def load_weights_device(self, t):
+        """The same load from a contiguous float32 torch tensor of num_params elements on the engine's device
+        (az_net_load_weights_device; state_dict_blob makes one): packed by kernels, no host trip.  Waits for
+        torch's current stream first -- the engine stream does not order with it -- and returns when the net
+        holds the new weights, so `t` may be overwritten."""
+        if (not hasattr(t, "data_ptr") or not getattr(t, "is_cuda", False) or str(t.dtype) != "torch.float32"
+                or not t.is_contiguous() or t.numel() != self.num_params):
+            raise ValueError(f"need a contiguous float32 device tensor of {self.num_params} elements")
+        import torch
+        torch.cuda.current_stream(t.device).synchronize()
+        check(lib().az_net_load_weights_device(self.h, ctypes.c_void_p(t.data_ptr()), t.numel()))
 
     def init_random(self, seed):
         check(lib().az_net_init_random(self.h, seed))

@@ -102,6 +102,7 @@ EXPORTS = {
     "az_net_destroy": (None, [vp]),
     "az_net_num_params": (c_int, [vp, P(c_size_t)]),
     "az_net_load_weights": (c_int, [vp, P(c_float), c_size_t]),
+    "az_net_load_weights_device": (c_int, [vp, vp, c_size_t]),
     "az_net_init_random": (c_int, [vp, c_uint64]),
     "az_net_get_weights": (c_int, [vp, P(c_float), c_size_t]),
     "az_net_set_precision": (c_int, [vp, c_int]),
@@ -113,6 +114,9 @@ EXPORTS = {
     "az_diag_net_plan": (c_int, [vp, ctypes.c_char_p, c_int]),
     "az_diag_device_mem": (c_int, [P(c_int64), P(c_int64)]),
     "az_diag_fail_alloc": (c_int, [c_int]),
+    "az_diag_net_fill_weights": (c_int, [vp, c_int]),
+    "az_diag_net_compare_weights": (c_int, [vp, vp, P(c_int), P(c_size_t)]),
+    "az_diag_net_pack_ms": (c_int, [vp, P(ctypes.c_double)]),
     "az_search_create": (c_int, [vp, vp, P(SearchCfg), P(vp)]),
     "az_search_destroy": (None, [vp]),
     "az_search_new_games": (c_int, [vp, P(c_int), c_int]),

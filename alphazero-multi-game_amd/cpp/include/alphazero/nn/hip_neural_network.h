@@ -29,6 +29,9 @@ class HipNeuralNetwork : public NeuralNetwork {
     HipNeuralNetwork& operator=(const HipNeuralNetwork&) = delete;
 
     void loadWeights(const std::vector<float>& blob);   // torch state_dict order, no num_batches_tracked
+    // the same blob in memory of the net's device (az_net_load_weights_device): packed by kernels, no host
+    // trip; the caller has finished writing d before the call, and may overwrite it after the return
+    void loadWeightsDevice(const float* d, size_t count);
     void initRandom(uint64_t seed);                      // counter-based init (oracle/net_oracle.init_blob)
     void setPrecision(int precision);
     // .azw file: "AZW1", 12 int32 NetShape fields, uint64 count, float32[count]

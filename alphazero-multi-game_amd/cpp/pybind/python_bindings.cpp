@@ -235,6 +235,9 @@ PYBIND11_MODULE(_alphazero_cpp, m) {
             std::vector<float> blob(a.data(), a.data() + a.size());
             self.loadWeights(blob);
         })
+        .def("loadWeightsDevice", [](nn::HipNeuralNetwork& self, uintptr_t ptr, size_t count) {
+            self.loadWeightsDevice(reinterpret_cast<const float*>(ptr), count);
+        }, py::arg("ptr"), py::arg("count"))
         .def("initRandom", &nn::HipNeuralNetwork::initRandom)
         .def("setPrecision", &nn::HipNeuralNetwork::setPrecision)
         .def("save", &nn::HipNeuralNetwork::save)

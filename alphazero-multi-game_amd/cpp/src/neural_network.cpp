@@ -77,6 +77,12 @@ void HipNeuralNetwork::loadWeights(const std::vector<float>& blob) {
     blob_ = blob;
 }
 
+void HipNeuralNetwork::loadWeightsDevice(const float* d, size_t count) {
+    std::lock_guard<std::mutex> lk(mu_);
+    check(az_net_load_weights_device(net_, d, count), "az_net_load_weights_device");
+    blob_.clear();
+}
+
 void HipNeuralNetwork::initRandom(uint64_t seed) {
     std::lock_guard<std::mutex> lk(mu_);
     check(az_net_init_random(net_, seed), "az_net_init_random");

@@ -84,12 +84,18 @@ struct az_net {
     float* rw_ws = nullptr;           // their split-K partials [rw_splits][rows][F]
     bool loaded = false;
     std::vector<float> host_blob;   // canonical blob of the loaded weights (az_net_get_weights)
+    // az_net_load_weights_device keeps the blob it loaded on the device (d_blob, in `blob`) and marks the
+    // host copy stale; az_net_get_weights / net_host_blob fetch it when first asked (net_load.hip)
+    float* d_blob = nullptr;
+    bool host_stale = false;
+    double pack_ms = -1.0;          // device time of the last device load's launches (profiling on), else -1
     // Device memory (dev_pool.h); the named pointers above and in the layers point into these.
     // weights: every weight buffer, in the loader's order (a load allocates what is missing and
     // rewrites the rest): what az_net_broadcast_weights sends.  acts: every activation / workspace
     // buffer (bytes before any zeroed tail): the poison diagnostic (az_diag_set_poison) overwrites
     // them before each forward.  misc: d_nb, ovf, zero, the router tables, the profile clock.
-    DevPool weights, acts, misc;
+    // blob: d_blob alone -- kept out of `weights`, whose list a broadcast compares and sends.
+    DevPool weights, acts, misc, blob;
     // profiling: HIP events bracketing the 3x3 trunk of every forward (on the launch stream)
     bool prof = false;
     ProfClock pc;                 // sampled trunk timing (az_net_profile)

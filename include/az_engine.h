@@ -121,6 +121,21 @@ void az_net_destroy(az_net* n);
  * eval form: weight, bias, running_mean, running_var per BN). */
 int az_net_num_params(az_net* n, size_t* count);
 int az_net_load_weights(az_net* n, const float* blob, size_t count);
+/* The same load from device memory: d_blob is the canonical fp32 blob (as az_net_load_weights takes,
+ * plain and rand-wire nets) in memory of the engine's device, e.g. a trainer's tensor.  Folding,
+ * conversion and every layout are made by kernels on the engine stream; no weight goes through the
+ * host.  Afterwards the net is in exactly the state az_net_load_weights leaves after loading the same
+ * values -- every weight buffer byte for byte, outputs, az_net_trunk_kernel and az_net_get_weights
+ * (which fetches the host copy of the blob when first asked) -- and az_net_set_precision works as
+ * after any load.  NaN weights are outside the bitwise contract: the host's and the device's fp16
+ * conversions may differ in a NaN's payload.
+ * Ordering: the engine stream is non-blocking, so it does not order with the stream that wrote
+ * d_blob.  The caller must have finished writing d_blob before the call (synchronise the writing
+ * stream first).  The call returns after the engine stream has run the load: d_blob may then be
+ * overwritten, and forwards and searches on this net see the new weights.  Other handles and
+ * streams of the process are not stalled.
+ * AZ_ERR_ARG for a null pointer or a wrong count, with the net unchanged. */
+int az_net_load_weights_device(az_net* n, const float* d_blob, size_t count);
 /* Counter-based deterministic init (SplitMix64), identical to tests' generator. */
 int az_net_init_random(az_net* n, uint64_t seed);
 /* The loaded weights as the canonical blob (count = az_net_num_params): what rank 0 broadcasts
@@ -152,6 +167,18 @@ int az_diag_device_mem(int64_t* bytes, int64_t* buffers);
  * AZ_ERR_OOM on the host, without touching the device, and disarms; -1 disarms.  Returns the
  * countdown it replaced (-1: none was armed). */
 int az_diag_fail_alloc(int nth);
+/* Diagnostic: every byte of every weight buffer of the net set to `byte` (buffers still missing are
+ * allocated first, as a broadcast's receiver does); whether the net counts as loaded does not change.
+ * A load afterwards must overwrite all of it. */
+int az_diag_net_fill_weights(az_net* n, int byte);
+/* Diagnostic: the weight buffers of two nets of one description compared byte for byte, padding
+ * included: *buffer = -1, *byte = 0 when all are equal, else the index of the first buffer that differs
+ * (allocation order) and the offset of its first differing byte; az_last_error then shows the 16 bytes
+ * around it of both nets.  AZ_ERR_ARG when the buffer lists differ. */
+int az_diag_net_compare_weights(az_net* a, az_net* b, int* buffer, size_t* byte);
+/* Diagnostic: the device time in ms of the last az_net_load_weights_device of this net, from its first to
+ * its last launch (HIP events, recorded only while az_net_profile is enabled); -1 when none was timed. */
+int az_diag_net_pack_ms(az_net* n, double* ms);
 /* predictBatch semantics: policy = softmax over A (max-subtracted, sequential fp32 sum,
  * torch_neural_network.cpp:296-316), value [B]. */
 int az_net_predict_batch(az_net* n, const float* planes, int B, float* policy, float* value);
