@@ -27,7 +27,7 @@ from ._lib import (AZ_GO_RULES_SET, AZ_MAX_LEAVES, GomokuRules, AZ_SEL_PROGRESSI
 __all__ = ["Engine", "HipNeuralNetwork", "ParallelMCTS", "SelfPlayManager", "Arena", "ArenaGameRecord", "EloRating", "GameRecord", "MoveData", "AzError",
            "Dataset", "TrainingExample", "GAME_GOMOKU", "GAME_GO", "ReplayBuffer", "replay_sym_cell", "replay_sample_plan",
            "AZ_PREC_F32", "AZ_PREC_BF16X3", "AZ_PREC_F16X3", "AZ_PREC_BF16", "AZ_PREC_FP16", "AZ_EVAL_NET", "AZ_EVAL_HASH", "AZ_EVAL_RANDOM", "AZ_EVAL_UNIFORM", "AZ_EVAL_CALLBACK",
-           "gomoku_net_desc", "state_dict_blob"]
+           "gomoku_net_desc", "state_dict_blob", "load_openings", "parse_openings"]
 
 _f = ctypes.POINTER(ctypes.c_float)
 _i = ctypes.POINTER(ctypes.c_int)
@@ -275,6 +275,31 @@ def widening_table(base, exponent, n_actions):
     return out
 
 
+def parse_openings(text, name="<openings>"):
+    """An openings file as a list of move sequences: one opening per line, whitespace-separated actions (Go's
+    pass is -1), `#` starts a comment, blank lines are ignored.  A malformed line raises ValueError with the
+    file's name and the line's number."""
+    book = []
+    for no, line in enumerate(text.splitlines(), 1):
+        words = line.split("#", 1)[0].split()
+        if not words:
+            continue
+        try:
+            seq = [int(w, 10) for w in words]
+        except ValueError:
+            raise ValueError(f"{name}:{no}: not a list of actions: {line.strip()!r}") from None
+        if min(seq) < -1:
+            raise ValueError(f"{name}:{no}: action {min(seq)} (the smallest is -1, Go's pass)")
+        book.append(seq)
+    return book
+
+
+def load_openings(path):
+    """parse_openings of a file: the sequences ParallelMCTS.new_games_moves takes."""
+    with open(path) as f:
+        return parse_openings(f.read(), str(path))
+
+
 class ParallelMCTS:
     """G independent ParallelMCTS trees (Mode S semantics, setDeterministicMode) on one device."""
 
@@ -355,6 +380,52 @@ class ParallelMCTS:
             ids = np.ascontiguousarray(ids, np.int32)
             assert ids.size == games.size
             check(lib().az_search_new_games_ids(self.h, games.ctypes.data, ids.ctypes.data, games.size))
+
+    def new_games_moves(self, sequences, games=None, ids=None):
+        """Fresh games in the listed slots (all by default), slot games[i] advanced by sequences[i] -- a list of
+        actions, Go's pass is -1 -- in one launch (az_search_new_games_moves): the handle as after newGames on
+        the same slots and ids and one updateWithMove per move.  An illegal move anywhere raises AzError
+        (AZ_ERR_ARG, naming the entry, the ply and the reason) and leaves the handle as it was."""
+        games = np.arange(self.G, dtype=np.int32) if games is None else np.ascontiguousarray(games, np.int32)
+        seqs = [np.asarray(q, np.int32).reshape(-1) for q in sequences]
+        if len(seqs) != games.size:
+            raise ValueError(f"{len(seqs)} sequences for {games.size} slots")
+        stride = max([q.size for q in seqs] + [1])
+        mv = np.full((max(1, len(seqs)), stride), AZ_ACTION_NONE, np.int32)
+        nm = np.zeros(max(1, len(seqs)), np.int32)
+        for i, q in enumerate(seqs):
+            mv[i, :q.size] = q
+            nm[i] = q.size
+        if ids is not None:
+            ids = np.ascontiguousarray(ids, np.int32)
+            assert ids.size == games.size
+        check(lib().az_search_new_games_moves(self.h, games.ctypes.data, ids.ctypes.data if ids is not None else None,
+                                              games.size, mv.ctypes.data, nm.ctypes.data, stride))
+
+    def setOpenings(self, book=None, random_plies=0, seed=0):
+        """The openings of the games the drivers start on this handle (az_search_set_openings): game `id` begins
+        with book[id % len(book)] -- book: a list of move sequences, e.g. load_openings(path) -- then plays up to
+        random_plies plies drawn on the device from the Philox stream (seed, id).  No book and no random plies:
+        empty-board starts again.  newGames / new_games_moves are not affected."""
+        from ._lib import OpeningsCfg
+        seqs = [np.asarray(q, np.int32).reshape(-1) for q in (book or [])]
+        if not seqs and not random_plies:
+            check(lib().az_search_set_openings(self.h, None))
+            return
+        stride = max([q.size for q in seqs] + [1])
+        mv = np.full((max(1, len(seqs)), stride), AZ_ACTION_NONE, np.int32)
+        nm = np.zeros(max(1, len(seqs)), np.int32)
+        for i, q in enumerate(seqs):
+            mv[i, :q.size] = q
+            nm[i] = q.size
+        cfg = OpeningsCfg(_ip(mv), _ip(nm), len(seqs), stride, int(random_plies), int(seed) & (2 ** 64 - 1))
+        check(lib().az_search_set_openings(self.h, ctypes.byref(cfg)))
+
+    def openings(self):
+        """(book size, random plies, seed) in force (az_search_openings); (0, 0, 0) with none."""
+        n, r, sd = ctypes.c_int(), ctypes.c_int(), ctypes.c_uint64()
+        check(lib().az_search_openings(self.h, ctypes.byref(n), ctypes.byref(r), ctypes.byref(sd)))
+        return n.value, r.value, sd.value
 
     def setNet(self, net):
         """ParallelMCTS::setNeuralNetwork on every slot (az_search_set_net); ends per-slot nets."""
@@ -636,6 +707,11 @@ class SelfPlayManager:
     def setProgressCallback(self, cb):
         self.progressCallback = cb
 
+    def setOpenings(self, book=None, random_plies=0, seed=0):
+        """Every game generateGames starts begins with an opening (ParallelMCTS.setOpenings); its plies head the
+        game's record as MoveData with an empty policy."""
+        self.mcts.setOpenings(book, random_plies, seed)
+
     def getTemperature(self, moveNum):
         return self.finalTemperature if moveNum >= self.temperatureDropMove else self.initialTemperature
 
@@ -778,6 +854,11 @@ class Arena:
         n = ctypes.c_int64(0)
         check(lib().az_arena_step(self.h, ctypes.byref(n)))
         return n.value
+
+    def setOpenings(self, book=None, random_plies=0, seed=0):
+        """Every game begins with an opening, both trees of its table alike (ParallelMCTS.setOpenings on the
+        arena's handle); with swap_colors games 2k and 2k + 1 play opening k with the colours swapped."""
+        self.search.setOpenings(book, random_plies, seed)
 
     def tableGames(self):
         """The game id each table plays now (-1: idle)."""

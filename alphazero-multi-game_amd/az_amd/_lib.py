@@ -49,6 +49,11 @@ class GomokuRules(ctypes.Structure):
     _fields_ = [("renju", c_int), ("omok", c_int), ("pro_long_opening", c_int)]
 
 
+class OpeningsCfg(ctypes.Structure):
+    _fields_ = [("moves", P(c_int)), ("n_moves", P(c_int)), ("n_openings", c_int), ("stride", c_int),
+                ("random_plies", c_int), ("seed", c_uint64)]
+
+
 AZ_GO_RULES_SET = 1
 AZ_SEL_UCB, AZ_SEL_PUCT, AZ_SEL_PROGRESSIVE_BIAS, AZ_SEL_RAVE = 0, 1, 2, 3
 AZ_MAX_LEAVES = 32   # az_search_set_leaves: the largest leaf parallelism
@@ -138,6 +143,9 @@ EXPORTS = {
     "az_search_simulate_masked": (c_int, [vp, c_int, vp]),
     "az_search_release_masked": (c_int, [vp, c_int, vp, vp]),
     "az_search_new_games_ids": (c_int, [vp, vp, vp, c_int]),
+    "az_search_new_games_moves": (c_int, [vp, vp, vp, c_int, vp, vp, c_int]),
+    "az_search_set_openings": (c_int, [vp, P(OpeningsCfg)]),
+    "az_search_openings": (c_int, [vp, P(c_int), P(c_int), P(c_uint64)]),
     "az_search_clear_tt": (c_int, [vp]),
     "az_search_set_rng": (c_int, [vp, c_int, vp]),
     "az_search_set_evaluator": (c_int, [vp, EVAL_FN, vp]),

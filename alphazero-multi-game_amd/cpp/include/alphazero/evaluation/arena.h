@@ -80,6 +80,11 @@ class Arena {
     int64_t step();                                           // one ply on every live table; moves played
     std::vector<ArenaGame> run(int totalGames, int maxMoves = 0);   // by game id
     ArenaSummary summary() const;
+    // Openings (az_search_set_openings on the arena's handle): every game begins with an opening of the book
+    // and / or random plies, both trees of its table alike; with swapColors games 2k and 2k + 1 play opening
+    // k % book.size() with the colours swapped.  The opening plies head a game's moves (empty policy), their
+    // movers follow the colour.  A refused book throws std::runtime_error.
+    void setOpenings(const std::vector<std::vector<int>>& book, int randomPlies = 0, uint64_t seed = 0);
     void setProgressCallback(std::function<void(int, int, int, int64_t)> cb) { progress_ = std::move(cb); }
     void setAbort(bool abort) { abort_ = abort ? 1 : 0; }
     az_arena* handle() const { return arena_; }

@@ -46,6 +46,11 @@ struct RunMetadata {
     long long jobTotalMoves = -1;
     double jobSeconds = -1.0;            // the slowest rank's generateGames time
     double jobMovesPerSecond = -1.0;
+    // openings (--openings / --random-opening-plies / --openings-seed): three more keys, written only by a run
+    // that used them
+    std::string openings;                // the openings file
+    int randomOpeningPlies = 0;
+    unsigned long long openingsSeed = 0;
 };
 
 // The file's text.

@@ -4,6 +4,7 @@
 // pool; records, progress callbacks, saved files and counters keep the reference's meaning.
 #pragma once
 #include <atomic>
+#include <cstdint>
 #include <functional>
 #include <string>
 #include <vector>
@@ -78,6 +79,16 @@ class SelfPlayManager {
     // generateGames fills `rb` (replay_buffer.h; same game type, board and device as the run, else generateGames
     // throws): every finished or cut game commits its positions.  Not owned; nullptr: none.
     void setReplayBuffer(ReplayBuffer* rb) { replay_ = rb; }
+    // Openings (az_search_set_openings): game `id` of a run begins with book[id % book.size()] (move sequences,
+    // e.g. core::loadOpenings; Go's pass is -1), then plays up to randomPlies plies drawn on the device from the
+    // Philox stream (seed, id); its record begins with those plies (empty policy, value 0).  An illegal opening
+    // makes generateGames throw.  An empty book and no random plies: games start from the empty board.
+    void setOpenings(std::vector<std::vector<int>> book, int randomPlies = 0, uint64_t seed = 0) {
+        book_ = std::move(book); randomPlies_ = randomPlies; openingsSeed_ = seed;
+    }
+    const std::vector<std::vector<int>>& getOpenings() const { return book_; }
+    int getRandomOpeningPlies() const { return randomPlies_; }
+    uint64_t getOpeningsSeed() const { return openingsSeed_; }
     void setSeeds(unsigned noiseSeed, int noiseSeedStride) { noiseSeed_ = noiseSeed; noiseStride_ = noiseSeedStride; }
     // Evaluation log (tests: a game replayed through the CPU oracle): every network evaluation of device
     // slot `slot` (the game id while the games fit the slots) -- post-softmax policy [NA], value, feature
@@ -114,6 +125,9 @@ class SelfPlayManager {
     int firstGame_ = 0;
     Distributed* dist_ = nullptr;
     ReplayBuffer* replay_ = nullptr;
+    std::vector<std::vector<int>> book_;
+    int randomPlies_ = 0;
+    uint64_t openingsSeed_ = 0;
     JobStats job_;
 };
 

@@ -16,6 +16,7 @@
 #include "alphazero/nn/random_policy_network.h"
 #include "alphazero/selfplay/dataset.h"
 #include "alphazero/selfplay/game_record.h"
+#include "alphazero/selfplay/openings.h"
 #include "alphazero/selfplay/replay_buffer.h"
 #include "alphazero/selfplay/distributed.h"
 #include "alphazero/selfplay/run_metadata.h"
@@ -549,8 +550,14 @@ PYBIND11_MODULE(_alphazero_cpp, m) {
         .def_readwrite("jobGamesCompleted", &selfplay::RunMetadata::jobGamesCompleted)
         .def_readwrite("jobTotalMoves", &selfplay::RunMetadata::jobTotalMoves)
         .def_readwrite("jobSeconds", &selfplay::RunMetadata::jobSeconds)
-        .def_readwrite("jobMovesPerSecond", &selfplay::RunMetadata::jobMovesPerSecond);
+        .def_readwrite("jobMovesPerSecond", &selfplay::RunMetadata::jobMovesPerSecond)
+        .def_readwrite("openings", &selfplay::RunMetadata::openings)
+        .def_readwrite("randomOpeningPlies", &selfplay::RunMetadata::randomOpeningPlies)
+        .def_readwrite("openingsSeed", &selfplay::RunMetadata::openingsSeed);
     m.def("runMetadataJson", &selfplay::runMetadataJson);
+    // the openings file (alphazero/selfplay/openings.h): a list of move sequences; a malformed line is a ValueError
+    m.def("parseOpenings", &selfplay::parseOpenings, py::arg("text"), py::arg("name") = "<openings>");
+    m.def("loadOpenings", &selfplay::loadOpenings, py::arg("path"));
     m.def("writeRunMetadata", &selfplay::writeRunMetadata, py::arg("metadata"), py::arg("outputDir"));
     py::class_<selfplay::GameShard>(m, "GameShard")
         .def(py::init<>())
@@ -614,6 +621,7 @@ PYBIND11_MODULE(_alphazero_cpp, m) {
             return self.run(totalGames, maxMoves);
         }, py::arg("totalGames"), py::arg("maxMoves") = 0)
         .def("summary", &evaluation::Arena::summary)
+        .def("setOpenings", &evaluation::Arena::setOpenings, py::arg("book"), py::arg("randomPlies") = 0, py::arg("seed") = 0)
         .def("setAbort", &evaluation::Arena::setAbort)
         .def("setProgressCallback", [](evaluation::Arena& self, std::function<void(int, int, int, int64_t)> cb) {
             self.setProgressCallback([cb](int g, int mv, int tg, int64_t tm) {
@@ -653,6 +661,11 @@ PYBIND11_MODULE(_alphazero_cpp, m) {
         .def("setMaxMoves", &selfplay::SelfPlayManager::setMaxMoves)
         .def("setReplayBuffer", &selfplay::SelfPlayManager::setReplayBuffer, py::arg("replayBuffer").none(true),
              py::keep_alive<1, 2>())
+        .def("setOpenings", &selfplay::SelfPlayManager::setOpenings, py::arg("book"), py::arg("randomPlies") = 0,
+             py::arg("seed") = 0)
+        .def("getOpenings", &selfplay::SelfPlayManager::getOpenings)
+        .def("getRandomOpeningPlies", &selfplay::SelfPlayManager::getRandomOpeningPlies)
+        .def("getOpeningsSeed", &selfplay::SelfPlayManager::getOpeningsSeed)
         .def("setSeeds", &selfplay::SelfPlayManager::setSeeds)
         .def("setShard", &selfplay::SelfPlayManager::setShard)
         .def("getFirstGameId", &selfplay::SelfPlayManager::getFirstGameId)

@@ -4,6 +4,8 @@
 #include <cmath>
 #include <stdexcept>
 
+#include "alphazero/selfplay/openings.h"
+
 namespace alphazero {
 namespace evaluation {
 
@@ -120,6 +122,10 @@ std::vector<ArenaGame> Arena::run(int totalGames, int maxMoves) {
     RunCtx ctx{&games, &progress_};
     check(az_arena_run(arena_, totalGames, maxMoves, sinkThunk, progressThunk, &ctx, &abort_), "az_arena_run");
     return games;
+}
+
+void Arena::setOpenings(const std::vector<std::vector<int>>& book, int randomPlies, uint64_t seed) {
+    selfplay::applyOpenings(az_arena_search(arena_), book, randomPlies, seed);
 }
 
 ArenaSummary Arena::summary() const {

@@ -310,12 +310,11 @@ void ParallelMCTS::rebuild() {
     }
     if (c.eval_kind == AZ_EVAL_CALLBACK) check(az_search_set_evaluator(s_, &ParallelMCTS::hostEvaluate, this), "az_search_set_evaluator");
     const int g0 = 0;
-    check(az_search_new_games(s_, &g0, 1), "az_search_new_games");
-    // a non-initial root: replay its history (each move a fresh root, as updateWithMove without a search)
-    for (int a : root_->getMoveHistory()) {
-        int t = 0, r = 0;
-        check(az_search_apply(s_, &a, &t, &r), "az_search_apply");
-    }
+    // a non-initial root: its history replayed on the device in one launch (the state one updateWithMove per
+    // move without a search would leave: a fresh root)
+    const std::vector<int> hist = root_->getMoveHistory();
+    const int nh = (int)hist.size();
+    check(az_search_new_games_moves(s_, &g0, nullptr, 1, hist.data(), &nh, nh), "az_search_new_games_moves");
     if (!rng.empty()) check(az_search_set_rng(s_, 0, rng.data()), "az_search_set_rng");
     searched_ = false;
 }

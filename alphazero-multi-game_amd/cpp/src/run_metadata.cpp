@@ -60,7 +60,13 @@ std::string runMetadataJson(const RunMetadata& m) {
     f << "  \"job_games_completed\": " << m.jobGamesCompleted << ",\n";
     f << "  \"job_total_moves\": " << m.jobTotalMoves << ",\n";
     f << "  \"job_seconds\": " << m.jobSeconds << ",\n";
-    f << "  \"job_moves_per_second\": " << m.jobMovesPerSecond << "\n";
+    const bool openings = !m.openings.empty() || m.randomOpeningPlies > 0;
+    f << "  \"job_moves_per_second\": " << m.jobMovesPerSecond << (openings ? ",\n" : "\n");
+    if (openings) {   // a run that started its games from openings (the file's keys are unchanged without)
+        f << "  \"openings\": " << quoted(m.openings) << ",\n";
+        f << "  \"random_opening_plies\": " << m.randomOpeningPlies << ",\n";
+        f << "  \"openings_seed\": " << m.openingsSeed << "\n";
+    }
     f << "}\n";
     return f.str();
 }

@@ -12,6 +12,7 @@
 #include "alphazero/games/gomoku/gomoku_state.h"
 #include "alphazero/nn/hip_neural_network.h"
 #include "alphazero/selfplay/distributed.h"
+#include "alphazero/selfplay/openings.h"
 #include "alphazero/selfplay/replay_buffer.h"
 
 namespace alphazero {
@@ -155,6 +156,14 @@ int SelfPlayManager::runGames(core::GameType type, int bs, bool variant, std::ve
     if (replay_ && az_search_attach_replay(s, replay_->handle())) {
         az_search_destroy(s);
         throw std::runtime_error(az_last_error());
+    }
+    if (!book_.empty() || randomPlies_ != 0) {
+        try {
+            applyOpenings(s, book_, randomPlies_, openingsSeed_);
+        } catch (...) {
+            az_search_destroy(s);
+            throw;
+        }
     }
     EvalCtx ectx{nn_, type, bs, variant};
     if (ev.kind == AZ_EVAL_CALLBACK && az_search_set_evaluator(s, host_eval, &ectx)) {

@@ -25,6 +25,7 @@
 #include "alphazero/evaluation/arena.h"
 #include "alphazero/nn/hip_neural_network.h"
 #include "alphazero/selfplay/game_record.h"
+#include "alphazero/selfplay/openings.h"
 
 using namespace alphazero;
 
@@ -66,6 +67,10 @@ void usage() {
                  "  --precision P           fp16 | f16x3 | bf16x3 | f32 (default: as loaded)\n"
                  "  --max-moves N           cut games at N moves\n"
                  "  --device D              HIP device (default LOCAL_RANK, else 0)\n"
+                 "  --openings FILE         openings book: one opening per line, whitespace-separated actions (Go's pass\n"
+                 "                          is -1), # comments; with --swap games 2k and 2k + 1 play opening k\n"
+                 "  --random-opening-plies N  random legal plies played after the book's, drawn on the device (default 0)\n"
+                 "  --openings-seed S       seed of the random opening plies (default 0)\n"
                  "Refused: --time-control, --variant, --game chess\n";
 }
 
@@ -147,6 +152,14 @@ int run(int argc, char** argv) {
     cfg.temperature = temperature;
     cfg.seed = (uint32_t)args.getInt("--seed", 42);
     evaluation::Arena arena(*netA, *netB, cfg);
+    const std::string openingsPath = args.get("--openings", "");
+    const int randomOpeningPlies = args.getInt("--random-opening-plies", 0);
+    const unsigned long long openingsSeed = args.has("--openings-seed") ? std::stoull(args.get("--openings-seed", "0")) : 0ULL;
+    if (randomOpeningPlies < 0) throw std::invalid_argument("--random-opening-plies");
+    const bool openings = !openingsPath.empty() || randomOpeningPlies > 0;
+    if (openings)
+        arena.setOpenings(openingsPath.empty() ? selfplay::OpeningBook{} : selfplay::loadOpenings(openingsPath), randomOpeningPlies,
+                          openingsSeed);
     const std::vector<evaluation::ArenaGame> recs = arena.run(games, maxMoves);
     const evaluation::ArenaSummary s = arena.summary();
 
@@ -181,8 +194,12 @@ int run(int argc, char** argv) {
        << "  \"time_control\": null,\n"
        << "  \"timestamp\": " << quoted(stamp) << ",\n"
        << "  \"avg_move_time\": " << jsonNumber(s.moves ? moveMs / 1000.0 / (double)s.moves : 0.0) << ",\n"
-       << "  \"total_moves\": " << s.moves << "\n"
-       << "}\n";
+       << "  \"total_moves\": " << s.moves << (openings ? ",\n" : "\n");
+    if (openings)   // after the reference's keys, and only for a match that used them
+        js << "  \"openings\": " << quoted(openingsPath) << ",\n"
+           << "  \"random_opening_plies\": " << randomOpeningPlies << ",\n"
+           << "  \"openings_seed\": " << openingsSeed << "\n";
+    js << "}\n";
     std::filesystem::create_directories(outputDir);
     const std::string file = (std::filesystem::path(outputDir) / (gameStr + "_" + shortA + "_vs_" + shortB + ".json")).string();
     std::ofstream f(file);

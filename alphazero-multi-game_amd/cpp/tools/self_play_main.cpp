@@ -31,6 +31,7 @@
 #include "alphazero/nn/hip_neural_network.h"
 #include "alphazero/nn/random_policy_network.h"
 #include "alphazero/selfplay/distributed.h"
+#include "alphazero/selfplay/openings.h"
 #include "alphazero/selfplay/run_metadata.h"
 #include "alphazero/selfplay/self_play_manager.h"
 
@@ -84,7 +85,11 @@ void usage() {
                  "  --precision P           fp16 | f16x3 | bf16x3 | f32\n"
                  "  --concurrent-games N    device game slots, at most --batch-size\n"
                  "  --max-moves N           cut games at N moves\n"
-                 "  --leaves K              leaf parallelism: K descents per game and step, one batch of slots x K (default 1)\n";
+                 "  --leaves K              leaf parallelism: K descents per game and step, one batch of slots x K (default 1)\n"
+                 "  --openings FILE         openings book: one opening per line, whitespace-separated actions (Go's pass\n"
+                 "                          is -1), # comments; game id begins with opening id % book size\n"
+                 "  --random-opening-plies N  random legal plies played after the book's, drawn on the device (default 0)\n"
+                 "  --openings-seed S       seed of the random opening plies (default 0)\n";
 }
 
 core::GameType gameTypeOf(const std::string& s) {
@@ -223,6 +228,13 @@ int run(int argc, char** argv) {
     if (args.has("--concurrent-games")) mgr.setConcurrentGames(args.getInt("--concurrent-games", batchSize));
     if (args.has("--max-moves")) mgr.setMaxMoves(args.getInt("--max-moves", 0));
     if (args.has("--leaves")) mgr.setLeafParallelism(args.getInt("--leaves", 1));
+    const std::string openingsPath = args.get("--openings", "");
+    const int randomOpeningPlies = args.getInt("--random-opening-plies", 0);
+    const unsigned long long openingsSeed = args.has("--openings-seed") ? std::stoull(args.get("--openings-seed", "0")) : 0ULL;
+    if (randomOpeningPlies < 0) throw std::invalid_argument("--random-opening-plies");
+    if (!openingsPath.empty() || randomOpeningPlies > 0)
+        mgr.setOpenings(openingsPath.empty() ? selfplay::OpeningBook{} : selfplay::loadOpenings(openingsPath), randomOpeningPlies,
+                        openingsSeed);
     mgr.setSaveGames(true, outputDir);
     mcts::MCTSConfig mc;
     mc.numThreads = numThreads;
@@ -295,6 +307,9 @@ int run(int argc, char** argv) {
     md.firstGameId = shard.firstGame;
     md.precision = hip ? precisionName(hip->shape().precision) : "";
     md.device = net->getDeviceInfo();
+    md.openings = openingsPath;
+    md.randomOpeningPlies = randomOpeningPlies;
+    md.openingsSeed = openingsSeed;
     if (dist) {
         const selfplay::JobStats& j = mgr.getJobStats();
         md.jobGamesCompleted = j.gamesCompleted;

@@ -46,14 +46,35 @@ bool a_first(const az_arena* a, int gid) { return !a->c.swap_colors || gid % 2 =
 
 int arena_start(az_arena* a, const std::vector<int>& tables) {
     if (tables.empty()) return 0;
-    std::vector<int> slots, ids;
+    std::vector<int> slots, ids, open_ids;
     for (int i : tables) {
         az_arena::Table& t = a->tab[i];
         t = az_arena::Table{};
         t.gid = a->next++;
-        for (int p = 0; p < 2; ++p) { slots.push_back(2 * i + p); ids.push_back(2 * t.gid + p); }
+        // az_search_set_openings: both trees of a table play one opening; with swap_colors games 2k and 2k + 1 share it
+        const int oid = a->c.swap_colors ? t.gid / 2 : t.gid;
+        for (int p = 0; p < 2; ++p) { slots.push_back(2 * i + p); ids.push_back(2 * t.gid + p); open_ids.push_back(oid); }
     }
-    return az_search_new_games_ids(a->s, slots.data(), ids.data(), (int)slots.size());
+    az_search* s = a->s;
+    std::vector<std::vector<int>> opened;
+    {
+        std::lock_guard<std::mutex> lk(s->mu);
+        HIPCHK(hipSetDevice(s->e->device));
+        if (int r = search_start_games(s, slots.data(), (int)slots.size(), ids.data(), open_ids.data(), &opened)) return r;
+    }
+    for (size_t k = 0; k < tables.size(); ++k) {
+        az_arena::Table& t = a->tab[tables[k]];
+        // the opening plies head the record (no search behind them); the mover is the net that owns the colour
+        for (int act : opened[2 * k]) {
+            const bool a_moves = (t.ply % 2 == 0) == a_first(a, t.gid);
+            t.pol.emplace_back();
+            t.cact.emplace_back();
+            t.moves.push_back(az_move_rec{act, 0.0f, 0, nullptr, nullptr, 0});
+            t.mover.push_back((uint8_t)(a_moves ? 0 : 1));
+            t.ply += 1;
+        }
+    }
+    return 0;
 }
 
 int arena_begin(az_arena* a, int total, int max_moves) {
@@ -99,7 +120,8 @@ int arena_finish(az_arena* a, int table, int result, bool cut) {
     const bool af = a_first(a, t.gid);
     // evaluate.py:259-278: player 1's win is the starter's
     const float score_a = result == 2 ? (af ? 1.0f : 0.0f) : result == 3 ? (af ? 0.0f : 1.0f) : 0.5f;
-    for (size_t i = 0; i < t.moves.size(); ++i) { t.moves[i].policy = t.pol[i].data(); t.moves[i].child_actions = t.cact[i].data(); }
+    for (size_t i = 0; i < t.moves.size(); ++i)
+        if (t.moves[i].n_children) { t.moves[i].policy = t.pol[i].data(); t.moves[i].child_actions = t.cact[i].data(); }
     a->sum.games += 1;
     a->sum.wins_a += score_a == 1.0f; a->sum.wins_b += score_a == 0.0f; a->sum.draws += score_a == 0.5f;
     a->sum.evals_a += ca[0]; a->sum.evals_b += cb[0];

@@ -98,6 +98,16 @@ struct az_search {
         std::vector<std::mt19937> rng;
         std::vector<float> noise;
     } pf;
+    // az_search_set_openings: the games the drivers start (az_selfplay_step restarts, az_selfplay_run, the
+    // arena) begin with an opening of the book and / or random plies; off: they start from the empty board and
+    // nothing more is launched.  The book lives on the host (records, mirrors) and in the handle's pool.
+    struct Openings {
+        bool on = false;
+        std::vector<int> moves, n_moves;   // [n][stride], [n]
+        int n = 0, stride = 0, rplies = 0;
+        uint64_t seed = 0;
+        int* d_moves = nullptr; int* d_nm = nullptr;
+    } op;
     std::mutex mu;
 };
 
@@ -111,6 +121,16 @@ int search_noise(az_search* s, float alpha, float eps, const uint8_t* mask);
 // stream id for the evaluator / noise seeds (default: the slot index), so a game's record
 // does not depend on which slot plays it.
 int search_new_games(az_search* s, const int* games, int n, const int* seed_ids = nullptr);
+// search_new_games with slot games[i] advanced by moves[i * stride .. i * stride + n_moves[i]), every move
+// judged against the rules first: an illegal one is AZ_ERR_ARG and nothing has changed.
+int search_open_games(az_search* s, const int* games, int n, const int* seed_ids, const int* moves, const int* n_moves,
+                      int stride);
+// The games a driver starts: search_new_games on a handle without openings; else entry i begins with opening
+// open_ids[i] % n_openings (open_ids null: its stream id) and the random plies of stream open_ids[i].
+// played (optional): per entry the opening plies its game was started with.
+int search_start_games(az_search* s, const int* games, int n, const int* seed_ids, const int* open_ids,
+                       std::vector<std::vector<int>>* played);
+int search_set_openings(az_search* s, const az_openings_cfg* cfg);
 int search_select(az_search* s, int training, const float* temps_host, float T, int* actions, float* values, float* probs,
                   int* cact, int* nch);
 // makeMove + updateWithMove (device), then subtree compaction into the other arena.

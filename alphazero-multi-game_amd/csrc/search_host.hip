@@ -471,6 +471,222 @@ int search_new_games(az_search* s, const int* games, int n, const int* seed_ids)
     return 0;
 }
 
+namespace {
+const char* open_reason(const az_search* s, int why) {
+    switch (why) {
+    case AZ_OPEN_RANGE: return "is out of range";
+    case AZ_OPEN_OCCUPIED: return "is an occupied cell";
+    case AZ_OPEN_FORBIDDEN: return s->t.renju ? "is forbidden to Black under the Renju rules" : "is forbidden to Black under the Omok rules";
+    case AZ_OPEN_SUICIDE: return "is suicide";
+    case AZ_OPEN_KO: return "retakes the ko";
+    case AZ_OPEN_SUPERKO: return "repeats a position (superko)";
+    case AZ_OPEN_ENDED: return "comes after the game has ended";
+    }
+    return "is illegal";
+}
+}  // namespace
+
+namespace {
+// One start through k_open_games: entry i starts slot games[i] with sequence seq_of[i] (null: i) of the
+// sequences (moves / n_moves / stride on the host, d_moves / d_nm the same on the device), then up to rplies
+// random plies of the Philox stream (seed, rand_ids[i] -- null: the seed id).
+struct OpenJob {
+    const int* games; const int* seed_ids; int n;
+    const int* moves; const int* n_moves; int stride;
+    const int* d_moves; const int* d_nm;
+    const int* seq_of; const int* rand_ids;
+    int rplies; uint64_t seed;
+};
+
+// validate: a dry pass judges every sequence first, so a refused call has changed nothing.
+// played (optional): per entry the plies its game was started with (the sequence, then the random picks).
+int open_games_run(az_search* s, const OpenJob& j, bool validate, std::vector<std::vector<int>>* played) {
+    hipStream_t st = s->e->stream;
+    const int n = j.n;
+    const bool keeps_hist = s->t.game == GAME_GO && s->t.superko;
+    int longest = 0;
+    for (int i = 0; i < n; ++i) longest = std::max(longest, j.n_moves ? j.n_moves[j.seq_of ? j.seq_of[i] : i] : 0);
+    DevPool tmp;   // freed on every return
+    int *d_seq = nullptr, *d_rid = nullptr, *d_picks = nullptr, *d_rep = nullptr;
+    uint64_t* d_hist = nullptr;
+    if (j.seq_of) if (int r = tmp.alloc(&d_seq, (size_t)n)) return r;
+    if (j.rand_ids) if (int r = tmp.alloc(&d_rid, (size_t)n)) return r;
+    if (j.rplies > 0) if (int r = tmp.alloc(&d_picks, (size_t)n * j.rplies)) return r;
+    if (int r = tmp.alloc(&d_rep, AZ_OPEN_REP * (size_t)n)) return r;
+    if (validate && keeps_hist) if (int r = tmp.alloc(&d_hist, (size_t)n * longest)) return r;
+    HIPCHK(hipMemcpyAsync(s->d_games, j.games, n * 4, hipMemcpyHostToDevice, st));
+    if (j.seed_ids) HIPCHK(hipMemcpyAsync(s->d_seed_ids, j.seed_ids, n * 4, hipMemcpyHostToDevice, st));
+    if (j.seq_of) HIPCHK(hipMemcpyAsync(d_seq, j.seq_of, n * 4, hipMemcpyHostToDevice, st));
+    if (j.rand_ids) HIPCHK(hipMemcpyAsync(d_rid, j.rand_ids, n * 4, hipMemcpyHostToDevice, st));
+    s->t.nd = s->arena[s->cur];
+    OpenDev o{};
+    o.games = s->d_games; o.seed_ids = j.seed_ids ? s->d_seed_ids : nullptr;
+    o.moves = j.d_moves; o.n_moves = j.d_nm; o.seq_of = d_seq; o.rand_ids = d_rid;
+    o.picks = d_picks; o.hist = d_hist; o.rep = d_rep;
+    o.n = n; o.stride = j.stride; o.hstride = longest;
+    o.key_lo = (uint32_t)j.seed; o.key_hi = (uint32_t)(j.seed >> 32); o.eval_seed = s->c.eval_seed;
+    std::vector<int> rep(AZ_OPEN_REP * (size_t)n), picks((size_t)n * std::max(j.rplies, 0));
+    if (validate) {
+        o.dry = 1; o.rplies = 0;                         // a random ply is legal by construction
+        hipLaunchKernelGGL(k_open_games, dim3(n), dim3(64), 0, st, s->t, o);
+        HIPCHK(hipGetLastError());
+        HIPCHK(hipMemcpyAsync(rep.data(), d_rep, rep.size() * 4, hipMemcpyDeviceToHost, st));
+        HIPCHK(hipStreamSynchronize(st));
+        for (int i = 0; i < n; ++i)
+            if (rep[AZ_OPEN_REP * i] >= 0) {
+                const int ply = rep[AZ_OPEN_REP * i], seq = j.seq_of ? j.seq_of[i] : i;
+                return az_fail(AZ_ERR_ARG, "entry %d (slot %d): ply %d, action %d %s", i, j.games[i], ply,
+                               j.moves[(size_t)seq * j.stride + ply], open_reason(s, rep[AZ_OPEN_REP * i + 1]));
+            }
+    }
+    o.dry = 0; o.rplies = j.rplies;
+    hipLaunchKernelGGL(k_open_games, dim3(n), dim3(64), 0, st, s->t, o);
+    hipLaunchKernelGGL(k_tt_clear, dim3(64, n), dim3(256), 0, st, s->t, s->d_games, n);
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipMemcpyAsync(rep.data(), d_rep, rep.size() * 4, hipMemcpyDeviceToHost, st));
+    if (j.rplies > 0) HIPCHK(hipMemcpyAsync(picks.data(), d_picks, picks.size() * 4, hipMemcpyDeviceToHost, st));
+    HIPCHK(hipStreamSynchronize(st));
+    if (played) played->assign(n, {});
+    for (int i = 0; i < n; ++i) {
+        const int g = j.games[i], seq = j.seq_of ? j.seq_of[i] : i;
+        const int nm = j.n_moves ? j.n_moves[seq] : 0, nr = rep[AZ_OPEN_REP * i + 4];
+        std::vector<int>& h = s->hist[g];
+        h.clear();
+        if (nm) h.assign(j.moves + (size_t)seq * j.stride, j.moves + (size_t)seq * j.stride + nm);
+        h.insert(h.end(), picks.begin() + (size_t)i * j.rplies, picks.begin() + (size_t)i * j.rplies + nr);
+        const int np = nm + nr;
+        // the mirrors as search_new_games and np search_apply_dev leave them (stones counts a Go pass too)
+        s->stones[g] = np; s->active[g] = rep[AZ_OPEN_REP * i + 2]; s->fresh[g] = np == 0; s->ply[g] = np;
+        if (np) s->used = true;                          // moves have been made (az_search_set_gomoku_rules comes before)
+        s->roots_ready = false;
+        const int id = j.seed_ids ? j.seed_ids[i] : g;
+        s->slot_id[g] = id;
+        s->sp_next_id = std::max(s->sp_next_id, id + 1);
+        pf_drop(s, g);
+        s->rng[g].seed(s->c.noise_seed + (uint32_t)(s->c.noise_seed_stride * id));
+        if (played) (*played)[i] = h;
+    }
+    if (s->replay) return replay_discard(s, j.games, n);   // a new game in the slot: its staged positions go
+    return 0;
+}
+}  // namespace
+
+// search_new_games with every listed slot advanced by its own move sequence (k_open_games): the handle as
+// after search_new_games and one az_search_apply per move.
+int search_open_games(az_search* s, const int* games, int n, const int* seed_ids, const int* moves, const int* n_moves,
+                      int stride) {
+    if (n <= 0) return 0;
+    const int G = s->c.n_games;
+    if (n > G) return az_fail(AZ_ERR_ARG, "%d slots listed, the handle has %d", n, G);
+    if (stride < 0) return az_fail(AZ_ERR_ARG, "stride %d", stride);
+    int longest = 0;
+    for (int i = 0; i < n; ++i) {
+        if (games[i] < 0 || games[i] >= G) return az_fail(AZ_ERR_ARG, "entry %d: game index %d out of range", i, games[i]);
+        if (n_moves[i] < 0 || n_moves[i] > stride)
+            return az_fail(AZ_ERR_ARG, "entry %d (slot %d): %d moves, the stride is %d", i, games[i], n_moves[i], stride);
+        longest = std::max(longest, n_moves[i]);
+    }
+    if (longest == 0) return search_new_games(s, games, n, seed_ids);
+    if (s->t.game == GAME_GO && s->t.superko)
+        for (int i = 0; i < n; ++i) {
+            int placed = 0;
+            for (int k = 0; k < n_moves[i]; ++k) placed += moves[(size_t)i * stride + k] >= 0;
+            if (placed > s->t.hmax)
+                return az_fail(AZ_ERR_CAPACITY, "entry %d (slot %d): %d stone moves, the position history holds %d", i, games[i],
+                               placed, s->t.hmax);
+        }
+    DevPool tmp;   // freed on every return
+    int *d_moves = nullptr, *d_nm = nullptr;
+    if (int r = tmp.alloc(&d_moves, (size_t)n * stride)) return r;
+    if (int r = tmp.alloc(&d_nm, (size_t)n)) return r;
+    HIPCHK(hipMemcpyAsync(d_moves, moves, (size_t)n * stride * 4, hipMemcpyHostToDevice, s->e->stream));
+    HIPCHK(hipMemcpyAsync(d_nm, n_moves, (size_t)n * 4, hipMemcpyHostToDevice, s->e->stream));
+    const OpenJob j{games, seed_ids, n, moves, n_moves, stride, d_moves, d_nm, nullptr, nullptr, 0, 0};
+    return open_games_run(s, j, true, nullptr);
+}
+
+// The games a driver starts: empty boards on a handle without openings (search_new_games, nothing more is
+// launched), else game i begins with opening open_ids[i] % n_openings of the book (null: its stream id) and
+// the random plies of stream open_ids[i] after it.  played (optional): per entry the opening plies.
+int search_start_games(az_search* s, const int* games, int n, const int* seed_ids, const int* open_ids,
+                       std::vector<std::vector<int>>* played) {
+    if (played) played->assign(std::max(n, 0), {});
+    if (!s->op.on) return search_new_games(s, games, n, seed_ids);
+    if (n <= 0) return 0;
+    for (int i = 0; i < n; ++i)
+        if (games[i] < 0 || games[i] >= s->c.n_games) return az_fail(AZ_ERR_ARG, "game index %d out of range", games[i]);
+    std::vector<int> seq(n), rid(n);
+    for (int i = 0; i < n; ++i) {
+        rid[i] = open_ids ? open_ids[i] : seed_ids ? seed_ids[i] : games[i];
+        seq[i] = s->op.n > 0 ? (int)((unsigned)rid[i] % (unsigned)s->op.n) : 0;
+    }
+    const OpenJob j{games, seed_ids, n, s->op.moves.data(), s->op.n > 0 ? s->op.n_moves.data() : nullptr, s->op.stride,
+                    s->op.d_moves, s->op.n > 0 ? s->op.d_nm : nullptr, seq.data(), rid.data(), s->op.rplies, s->op.seed};
+    return open_games_run(s, j, false, played);            // the book was judged when it was set
+}
+
+// The openings of the games the drivers start (az_search_set_openings); cfg null or empty: none.
+int search_set_openings(az_search* s, const az_openings_cfg* cfg) {
+    const bool go = s->t.game == GAME_GO;
+    if (!cfg || (cfg->n_openings == 0 && cfg->random_plies == 0)) {
+        s->pool.release(s->op.d_moves); s->pool.release(s->op.d_nm);
+        s->op = az_search::Openings{};
+        return 0;
+    }
+    const int n = cfg->n_openings, stride = cfg->stride;
+    if (n < 0 || cfg->random_plies < 0 || (n > 0 && (!cfg->moves || !cfg->n_moves || stride < 0)))
+        return az_fail(AZ_ERR_ARG, "openings: %d openings, stride %d, %d random plies", n, stride, cfg->random_plies);
+    int longest = 0;
+    for (int i = 0; i < n; ++i) {
+        if (cfg->n_moves[i] < 0 || cfg->n_moves[i] > stride)
+            return az_fail(AZ_ERR_ARG, "opening %d: %d moves, the stride is %d", i, cfg->n_moves[i], stride);
+        longest = std::max(longest, cfg->n_moves[i]);
+    }
+    if (go && s->t.superko && longest + cfg->random_plies > s->t.hmax)
+        return az_fail(AZ_ERR_CAPACITY, "openings of %d + %d plies, the position history holds %d", longest, cfg->random_plies,
+                       s->t.hmax);
+    hipStream_t st = s->e->stream;
+    DevPool fresh;   // the new book; adopted by the handle's pool once it is judged
+    int *d_moves = nullptr, *d_nm = nullptr;
+    if (n > 0) {
+        if (int r = fresh.alloc(&d_moves, (size_t)n * stride)) return r;
+        if (int r = fresh.alloc(&d_nm, (size_t)n)) return r;
+        HIPCHK(hipMemcpyAsync(d_moves, cfg->moves, (size_t)n * stride * 4, hipMemcpyHostToDevice, st));
+        HIPCHK(hipMemcpyAsync(d_nm, cfg->n_moves, (size_t)n * 4, hipMemcpyHostToDevice, st));
+        // every opening through the dry kernel: legal, and the game still playing after it
+        DevPool tmp;
+        int* d_rep = nullptr;
+        uint64_t* d_hist = nullptr;
+        if (int r = tmp.alloc(&d_rep, AZ_OPEN_REP * (size_t)n)) return r;
+        if (go && s->t.superko) if (int r = tmp.alloc(&d_hist, (size_t)n * longest)) return r;
+        OpenDev o{};
+        o.moves = d_moves; o.n_moves = d_nm; o.hist = d_hist; o.rep = d_rep;
+        o.n = n; o.stride = stride; o.hstride = longest; o.dry = 1;
+        std::vector<int> rep(AZ_OPEN_REP * (size_t)n);
+        hipLaunchKernelGGL(k_open_games, dim3(n), dim3(64), 0, st, s->t, o);
+        HIPCHK(hipGetLastError());
+        HIPCHK(hipMemcpyAsync(rep.data(), d_rep, rep.size() * 4, hipMemcpyDeviceToHost, st));
+        HIPCHK(hipStreamSynchronize(st));
+        for (int i = 0; i < n; ++i) {
+            const int* r = rep.data() + AZ_OPEN_REP * i;
+            if (r[0] >= 0)
+                return az_fail(AZ_ERR_ARG, "opening %d: ply %d, action %d %s", i, r[0], cfg->moves[(size_t)i * stride + r[0]],
+                               open_reason(s, r[1]));
+            if (!r[2]) return az_fail(AZ_ERR_ARG, "opening %d ends the game (result %d)", i, r[3]);
+        }
+    }
+    s->pool.release(s->op.d_moves); s->pool.release(s->op.d_nm);
+    s->pool.adopt(fresh);
+    s->op = az_search::Openings{};
+    s->op.on = true; s->op.n = n; s->op.stride = stride; s->op.rplies = cfg->random_plies; s->op.seed = cfg->seed;
+    if (n > 0) {
+        s->op.moves.assign(cfg->moves, cfg->moves + (size_t)n * stride);
+        s->op.n_moves.assign(cfg->n_moves, cfg->n_moves + n);
+    }
+    s->op.d_moves = d_moves; s->op.d_nm = d_nm;
+    return 0;
+}
+
 int search_select(az_search* s, int training, const float* temps_host, float T, int* actions, float* values, float* probs,
                   int* cact, int* nch) {
     hipStream_t st = s->e->stream;
@@ -888,6 +1104,31 @@ int az_search_new_games_ids(az_search* s, const int* games, const int* seed_ids,
     return search_new_games(s, games, n, seed_ids);
 }
 
+int az_search_new_games_moves(az_search* s, const int* games, const int* seed_ids, int n, const int* moves,
+                              const int* n_moves, int stride) {
+    if (!s || (!games && n > 0) || (!n_moves && n > 0)) return az_fail(AZ_ERR_ARG, "null argument");
+    if (!moves && n > 0 && stride > 0) return az_fail(AZ_ERR_ARG, "null argument");
+    std::lock_guard<std::mutex> lk(s->mu);
+    HIPCHK(hipSetDevice(s->e->device));
+    return search_open_games(s, games, n, seed_ids, moves, n_moves, stride);
+}
+
+int az_search_set_openings(az_search* s, const az_openings_cfg* cfg) {
+    if (!s) return az_fail(AZ_ERR_ARG, "null search");
+    std::lock_guard<std::mutex> lk(s->mu);
+    HIPCHK(hipSetDevice(s->e->device));
+    return search_set_openings(s, cfg);
+}
+
+int az_search_openings(az_search* s, int* n_openings, int* random_plies, uint64_t* seed) {
+    if (!s) return az_fail(AZ_ERR_ARG, "null search");
+    std::lock_guard<std::mutex> lk(s->mu);
+    if (n_openings) *n_openings = s->op.n;
+    if (random_plies) *random_plies = s->op.rplies;
+    if (seed) *seed = s->op.seed;
+    return 0;
+}
+
 int az_search_select_action(az_search* s, int game, int training, float temperature, int batch_inference,
                             const int* legal, int n_legal, int* action) {
     if (!s || !action || game < 0 || game >= s->c.n_games || n_legal < 0 || (n_legal > 0 && !legal))
@@ -965,6 +1206,16 @@ int az_search_apply(az_search* s, const int* actions, int* terminal, int* result
         for (int g = 0; g < G; ++g)
             if (bad[g]) return az_fail(AZ_ERR_ARG, "action %d of game %d is forbidden to Black under the %s rules", actions[g], g,
                                        s->t.renju ? "Renju" : "Omok");
+    }
+    if (s->t.game == GAME_GO) {
+        // GoState::makeMove throws on a move that is not legal: refused before anything moves
+        std::vector<int> bad(G);
+        hipLaunchKernelGGL(k_go_illegal_moves, dim3(G), dim3(64), 0, s->e->stream, s->t, s->d_actions, s->d_nch);
+        HIPCHK(hipGetLastError());
+        HIPCHK(hipMemcpyAsync(bad.data(), s->d_nch, G * 4, hipMemcpyDeviceToHost, s->e->stream));
+        HIPCHK(hipStreamSynchronize(s->e->stream));
+        for (int g = 0; g < G; ++g)
+            if (bad[g]) return az_fail(AZ_ERR_ARG, "action %d of game %d %s", actions[g], g, open_reason(s, bad[g]));
     }
     return search_apply_dev(s, terminal, result);
 }

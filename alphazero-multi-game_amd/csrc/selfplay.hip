@@ -79,7 +79,7 @@ int az_selfplay_step(az_search* s, const az_selfplay_cfg* cfg, int64_t* moves_do
             // it seeds -- as az_selfplay_run hands out ids -- rather than replaying its slot's seed
             std::vector<int> ids(fin.size());
             for (size_t i = 0; i < fin.size(); ++i) ids[i] = s->sp_next_id + (int)i;
-            if (int r = search_new_games(s, fin.data(), (int)fin.size(), ids.data())) return r;
+            if (int r = search_start_games(s, fin.data(), (int)fin.size(), ids.data(), nullptr, nullptr)) return r;   // openings, if set
             std::vector<uint8_t> m(G, 0);
             for (int g : fin) m[g] = 1;
             if (int r = search_noise(s, s->c.dirichlet_alpha, s->c.dirichlet_eps, m.data())) return r;
@@ -143,7 +143,18 @@ int az_selfplay_run(az_search* s, const az_selfplay_cfg* cfg, int total_games, i
             rec[slots[i]] = Rec{};
             mask[slots[i]] = 1;
         }
-        if (int r = search_new_games(s, slots.data(), (int)slots.size(), ids.data())) return r;
+        // from the empty board, or -- az_search_set_openings -- from the game's opening: its plies head the record
+        // (no search behind them: value 0, no children) and the start noise goes on the opened root
+        std::vector<std::vector<int>> opened;
+        if (int r = search_start_games(s, slots.data(), (int)slots.size(), ids.data(), nullptr, &opened)) return r;
+        for (size_t i = 0; i < slots.size(); ++i) {
+            Rec& R = rec[slots[i]];
+            for (int a : opened[i]) {
+                R.pol.emplace_back();
+                R.cact.emplace_back();
+                R.moves.push_back(az_move_rec{a, 0.0f, 0, nullptr, nullptr, 0});
+            }
+        }
         return search_noise(s, s->c.dirichlet_alpha, s->c.dirichlet_eps, mask.data());   // :184
     };
     if (s->replay)   // positions staged by earlier calls belong to games this run abandons
@@ -196,7 +207,8 @@ int az_selfplay_run(az_search* s, const az_selfplay_cfg* cfg, int total_games, i
         }
         for (int g : done) {
             Rec& R = rec[g];
-            for (size_t i = 0; i < R.moves.size(); ++i) { R.moves[i].policy = R.pol[i].data(); R.moves[i].child_actions = R.cact[i].data(); }
+            for (size_t i = 0; i < R.moves.size(); ++i)
+                if (R.moves[i].n_children) { R.moves[i].policy = R.pol[i].data(); R.moves[i].child_actions = R.cact[i].data(); }
             const int result = s->active[g] ? 0 : res[g];
             if (s->active[g]) {                     // cut at max_moves: park the slot
                 s->active[g] = 0;

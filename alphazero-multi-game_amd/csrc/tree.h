@@ -29,6 +29,9 @@ enum { ERR_NODES = 1, ERR_PATH = 2, ERR_RING = 4, ERR_BATCH = 8, ERR_HIST = 16, 
 // MCTSNodeSelection (include/alphazero/mcts/parallel_mcts.h:26-31); RAVE plays PUCT (selectChildRave)
 enum { SEL_UCB = 0, SEL_PUCT = 1, SEL_PROGRESSIVE_BIAS = 2, SEL_RAVE = 3 };
 enum { GAME_GOMOKU = 0, GAME_GO = 1 };
+// why k_open_games / k_go_illegal_moves refuse a move (0: legal)
+enum { AZ_OPEN_RANGE = 1, AZ_OPEN_OCCUPIED = 2, AZ_OPEN_FORBIDDEN = 3, AZ_OPEN_SUICIDE = 4, AZ_OPEN_KO = 5,
+       AZ_OPEN_SUPERKO = 6, AZ_OPEN_ENDED = 7 };
 
 struct Nodes {          // one arena: [G][ncap]
     int* N; float* W; int* VL; float* P; int* first; int16_t* act; int16_t* cnt; uint8_t* flag;
@@ -120,6 +123,22 @@ static_assert(offsetof(TreeDev, wid_tab) == offsetof(TreeDev, sel) + 8 * sizeof(
 static_assert(offsetof(TreeDev, sel) == offsetof(TreeDev, log_n) + sizeof(int*), "TreeDev hole before sel");
 static_assert(offsetof(TreeDev, stamp_game) == offsetof(TreeDev, wid_tab) + sizeof(int*), "TreeDev hole after wid_tab");
 static_assert(offsetof(TreeDev, tt_mask) == 10 * sizeof(int), "TreeDev hole before tt_mask");
+
+// k_open_games' arguments: entry i of n starts slot games[i] and plays sequence seq_of[i] (null: i) -- the
+// n_moves[seq] moves at moves[seq * stride] -- then up to rplies random plies of the Philox stream
+// (key_lo, key_hi) with id rand_ids[i] (null: the seed id).
+#define AZ_OPEN_REP 5         // ints of rep per entry: first bad ply (-1 none), reason, playing, GameResult, random plies
+struct OpenDev {
+    const int* games;        // [n] slots (a dry pass reads none: may be null)
+    const int* seed_ids;     // [n] evaluator / noise stream ids, null: the slot index
+    const int* moves; const int* n_moves; const int* seq_of;
+    const int* rand_ids;
+    int* picks;              // [n][rplies] the random plies played (null: not reported)
+    uint64_t* hist;          // dry: [n][hstride] Go position history of the pass
+    int* rep;                // [n][AZ_OPEN_REP]
+    int n, stride, dry, rplies, hstride;
+    uint32_t key_lo, key_hi, eval_seed;
+};
 
 // Replay buffer (az_replay_*, replay.hip): action-space training targets kept on the device.  A position is
 // a record of `rec` bytes -- board [A] u8, Go: min(10, liberties) [A] u8, then at `moff` (4-aligned) eight

@@ -30,6 +30,11 @@ __global__ void k_leaf_moves(TreeDev t, int* moves, int* len);
 __global__ void k_prune(TreeDev t, Nodes dst, int* src_of, int thr_all, const int* thr_g, long long* pruned);
 __global__ void k_noise(TreeDev t, const float* noise, const uint8_t* mask, float eps);
 __global__ void k_new_games(TreeDev t, const int* games, const int* seed_ids, int n, uint32_t eval_seed);
+// Go: bad[g] = the AZ_OPEN_* reason the rules refuse actions[g] of game g for (0: legal, a pass, no move)
+__global__ void k_go_illegal_moves(TreeDev t, const int* actions, int* bad);
+// openings (OpenDev, tree.h): fresh games in the listed slots, each advanced by a move sequence with every move
+// judged against the rules, then by random plies drawn on the device; dry: nothing of the slots is written
+__global__ void k_open_games(TreeDev t, OpenDev o);
 __global__ void k_init_slots(TreeDev t, Nodes other);
 __global__ void k_tt_clear(TreeDev t, const int* games, int n);
 __global__ void k_root_nchild(TreeDev t, int* out);

@@ -630,12 +630,11 @@ __device__ void go_write_leafrec(const TreeDev& t, int g, int lane, const uint8_
 // getLegalMoves (go_state.cpp:116-160): pass, then every empty non-ko point that is not suicide
 // (GoRules::isSuicidalMove) and whose resulting position -- same side to move, the old ko point --
 // is not in position_history_ (root history + the path's pushes; enforce_superko only).  Needs go_groups().
-__device__ int go_legal(const TreeDev& t, int g, int lane, const uint8_t* b, const GoLds& L, int player, int ko,
-                        uint64_t bh, int* legal, const GoKeys& K) {
+// rh[0, nr): the position history the candidates are held against (go_legal: the game's root history)
+__device__ __forceinline__ int go_legal_hist(const TreeDev& t, const uint64_t* rh, const int nr, int lane, const uint8_t* b,
+                                             const GoLds& L, int player, int ko, uint64_t bh, int* legal, const GoKeys& K) {
     const int A = t.A, bs = t.bs;
     const int opp = 3 - player;
-    const uint64_t* rh = t.rposh + (size_t)g * t.hmax;
-    const int nr = t.superko ? t.rnposh[g] : 0;
     const uint64_t tail = t.zplayer[player - 1] ^ (ko >= 0 ? t.zko[ko] : 0ULL) ^ t.zconst;
     if (lane == 0) legal[0] = -1;
     int n = 1;
@@ -685,6 +684,10 @@ __device__ int go_legal(const TreeDev& t, int g, int lane, const uint8_t* b, con
     }
     __syncthreads();
     return n;
+}
+__device__ int go_legal(const TreeDev& t, int g, int lane, const uint8_t* b, const GoLds& L, int player, int ko,
+                        uint64_t bh, int* legal, const GoKeys& K) {
+    return go_legal_hist(t, t.rposh + (size_t)g * t.hmax, t.superko ? t.rnposh[g] : 0, lane, b, L, player, ko, bh, legal, K);
 }
 
 }  // namespace
@@ -2057,6 +2060,230 @@ __global__ __launch_bounds__(64) void k_new_games(TreeDev t, const int* games, c
             // std::mt19937(seed + g) seeding (libstdc++ mersenne_twister_engine::seed)
             uint32_t* st = t.mt + (size_t)g * 625;
             st[0] = eval_seed + (uint32_t)(seed_ids ? seed_ids[idx] : g);
+            for (int i = 1; i < 624; ++i) st[i] = 1812433253u * (st[i - 1] ^ (st[i - 1] >> 30)) + (uint32_t)i;
+            st[624] = 624;
+        }
+    }
+}
+
+namespace {
+// One Go stone move against the rules, as getLegalMoves judges its candidates (go_legal above: the same
+// suicide test and the same resulting-position hash -- the mover to move, the old ko point -- against the
+// position history hist[0, nh)).  go_groups(.., &keys) must have run on the board; every lane of the wave
+// calls it with the same arguments and gets the same answer: an AZ_OPEN_* reason, 0 when the move is legal.
+__device__ int go_move_reason(const TreeDev& t, const uint8_t* b, const GoLds& L, int lane, int a, int player, int ko,
+                              uint64_t bh, const uint64_t* hist, int nh) {
+    const int A = t.A;
+    if (b[a] != 0) return AZ_OPEN_OCCUPIED;
+    if (a == ko) return AZ_OPEN_KO;
+    int nb[4], capg[4], nc = 0;
+    const int k = go_adj(a, t.bs, A, nb);
+    bool alive = false;
+    uint64_t h = bh ^ t.zpiece[(size_t)(player - 1) * A + a];
+    for (int q = 0; q < k; ++q) {
+        const int e = nb[q], v = b[e];
+        if (v == 0) { alive = true; continue; }
+        const int gi = L.gid[e];
+        if (v == player) { if (L.glib[gi] >= 2) alive = true; continue; }
+        if (L.glib[gi] == 1) {                    // its only liberty is a: captured
+            bool dup = false;
+            for (int r = 0; r < nc; ++r) dup |= capg[r] == gi;
+            if (!dup) { capg[nc++] = gi; h ^= L.gxor[gi]; }
+        }
+    }
+    if (!alive && nc == 0) return AZ_OPEN_SUICIDE;
+    if (!t.superko) return 0;
+    const uint64_t hc = h ^ t.zplayer[player - 1] ^ (ko >= 0 ? t.zko[ko] : 0ULL) ^ t.zconst;
+    bool hit = false;
+    for (int r = lane; r < nh; r += 64) hit |= hist[r] == hc;
+    return __ballot(hit) != 0ULL ? AZ_OPEN_SUPERKO : 0;
+}
+}  // namespace
+
+// Go: the moves az_search_apply is about to commit, against the rules (occupied point, suicide, the ko
+// point, a superko repeat) -- bad[g] = the AZ_OPEN_* reason, 0 for a legal move, a pass, a skipped or a
+// finished game.  One wave per game.
+__global__ __launch_bounds__(64) void k_go_illegal_moves(TreeDev t, const int* actions, int* bad) {
+    const int g = blockIdx.x;
+    const int lane = threadIdx.x;
+    __shared__ uint8_t board[AZ_MAXA];
+    __shared__ GoLds gl;
+    if (g >= t.G) return;
+    const int a = actions[g], A = t.A;
+    if (!t.active[g] || a < 0 || a >= A) { if (lane == 0) bad[g] = 0; return; }
+    const uint8_t* rb = t.rboard + (size_t)g * A;
+    for (int i = lane; i < A; i += 64) board[i] = rb[i];
+    __syncthreads();
+    const int p = t.rplayer[g];
+    GoKeys gk;
+    go_keys(t, board, p, lane, gk);
+    go_groups(t, board, gl, lane, 64, &gk);
+    const int why = go_move_reason(t, board, gl, lane, a, p, t.rko[g], t.rhash[g], t.rposh + (size_t)g * t.hmax,
+                                   t.superko ? t.rnposh[g] : 0);
+    if (lane == 0) bad[g] = why;
+}
+
+// Openings: fresh games in the listed slots, each advanced by its own move sequence in one launch -- what
+// k_new_games and one k_apply (+ k_compact) per move leave behind, field for field, with every move judged
+// against the rules first.  One wave per listed slot; the board lives in LDS as in k_apply, Go's captures
+// stay on lane 0 (go_play_seq).  o.rep[AZ_OPEN_REP idx ..]: {first bad ply or -1, its AZ_OPEN_* reason, the
+// game still playing after the opening, its GameResult, the random plies played}.  dry: the same pass without a
+// single store to the slot (Go's position history then grows in o.hist, o.hstride per entry, instead of the
+// slot's own); the host validates with it, so the storing pass never meets a bad move.
+// Random plies: after the sequence up to o.rplies further plies are drawn here.  Ply j (the game's real ply
+// number) of the game with stream id `id` draws Philox4x32-10 with key (o.key_lo, o.key_hi) and counter
+// (id, j, 0, 0) and plays legal[(out0 * n_legal) >> 32] of the side to move's legal moves in ascending order
+// (Gomoku: the empty cells less the forbidden ones; Go: go_legal's set without the pass).  A pick that would
+// end the game is not played and the opening stops there, as it does at an empty list: random plies never end
+// a game.  o.picks[o.rplies idx ..] are the plies played.
+__global__ __launch_bounds__(64) void k_open_games(TreeDev t, OpenDev o) {
+    const int idx = blockIdx.x;
+    const int lane = threadIdx.x;
+    __shared__ uint8_t board[AZ_MAXA];
+    __shared__ GoLds gl;
+    __shared__ uint64_t forb[AZ_FORB_WORDS];
+    __shared__ int legal[AZ_MAXNA];
+    __shared__ struct { uint64_t bh; int ko, passes, cap[2], nh, res; } S;
+    const int n = o.n, dry = o.dry;
+    if (idx >= n) return;
+    const int g = o.games ? o.games[idx] : 0;
+    const int A = t.A;
+    const bool go = t.game == GAME_GO;
+    const bool rules = !go && (t.renju || t.omok);
+    const int seq = o.seq_of ? o.seq_of[idx] : idx;
+    const int nm = o.n_moves ? o.n_moves[seq] : 0;
+    const int* mv = o.moves + (size_t)seq * o.stride;
+    const int sid = o.seed_ids ? o.seed_ids[idx] : g;
+    const uint32_t rid = (uint32_t)(o.rand_ids ? o.rand_ids[idx] : sid);
+    int* rep = o.rep + AZ_OPEN_REP * idx;
+    uint64_t* ph = dry ? o.hist + (size_t)idx * o.hstride : t.rposh + (size_t)g * t.hmax;
+    for (int i = lane; i < A; i += 64) board[i] = 0;
+    // the game's state, the same on every lane (Go: lane 0 plays, the others read S after the barrier)
+    int p = 1, stones = 0, res = R_ONGOING, ko = -1, passes = 0, nh = 0, cap0 = 0, cap1 = 0;
+    int h6[6] = {-1, -1, -1, -1, -1, -1};
+    uint64_t hash = go ? 0ULL : rules ? t.zplayer[0] ^ t.zconst : t.zplayer[0];
+    int bad = -1, why = 0, nrand = 0;
+    if (lane == 0) gl.nph = 0;                    // go_legal_hist: no path pushes, the history is ph[0, nh)
+    __syncthreads();
+    for (int i = 0; i < nm + o.rplies; ++i) {
+        int a;
+        if (i >= nm) {
+            // a random ply: the side to move's legal moves in ascending order, one picked by the game's stream
+            if (res != R_ONGOING) break;
+            uint32_t c[4] = {rid, (uint32_t)i, 0u, 0u}, k0 = o.key_lo, k1 = o.key_hi;
+            for (int round = 0; round < 10; ++round) {          // Philox4x32-10, as the replay plan's (replay.hip)
+                const uint64_t p0 = (uint64_t)0xD2511F53u * c[0], p1 = (uint64_t)0xCD9E8D57u * c[2];
+                const uint32_t n0 = (uint32_t)(p1 >> 32) ^ c[1] ^ k0, n2 = (uint32_t)(p0 >> 32) ^ c[3] ^ k1;
+                c[0] = n0; c[1] = (uint32_t)p1; c[2] = n2; c[3] = (uint32_t)p0;
+                k0 += 0x9E3779B9u; k1 += 0xBB67AE85u;
+            }
+            int nl;
+            if (go) {
+                GoKeys gk;
+                go_keys(t, board, p, lane, gk);
+                go_groups(t, board, gl, lane, 64, &gk);
+                nl = go_legal_hist(t, ph, t.superko ? nh : 0, lane, board, gl, p, ko, hash, legal, gk) - 1;   // [0]: the pass
+                if (nl <= 0) break;
+                a = legal[1 + (int)(((uint64_t)c[0] * (uint64_t)nl) >> 32)];
+            } else {
+                const bool masked = rules && p == 1;
+                if (masked) forbidden_mask_wave(t, board, lane, forb);
+                __syncthreads();
+                nl = 0;
+                for (int c0 = 0; c0 < A; c0 += 64) {
+                    const int q = c0 + lane;
+                    const bool ok = q < A && board[q] == 0 && !(masked && (forb[c0 >> 6] >> lane & 1ULL));
+                    const unsigned long long m = __ballot(ok);
+                    if (ok) legal[nl + __popcll(m & ((1ULL << lane) - 1ULL))] = q;
+                    nl += __popcll(m);
+                }
+                __syncthreads();
+                if (nl <= 0) break;
+                a = legal[(int)(((uint64_t)c[0] * (uint64_t)nl) >> 32)];
+            }
+        } else {
+            a = mv[i];
+        }
+        if (i >= nm) why = 0;
+        else if (res != R_ONGOING) why = AZ_OPEN_ENDED;
+        else if (a < (go ? -1 : 0) || a >= A) why = AZ_OPEN_RANGE;
+        else if (go) {
+            if (a >= 0) {
+                GoKeys gk;
+                go_keys(t, board, p, lane, gk);
+                go_groups(t, board, gl, lane, 64, &gk);
+                why = go_move_reason(t, board, gl, lane, a, p, ko, hash, ph, nh);
+            }
+        } else if (board[a] != 0) why = AZ_OPEN_OCCUPIED;
+        else if (rules && p == 1) {
+            const bool base = __ballot(gomoku_base_shapes(board, t.bs, t.renju, t.omok, lane, 64)) != 0ULL;
+            if (gomoku_forbidden(board, t.bs, t.renju, t.omok, a, base)) why = AZ_OPEN_FORBIDDEN;
+        }
+        if (why) { bad = i; break; }
+        if (go) {
+            // GoState::makeMove, as k_apply
+            go_clear_marks(gl, A, lane);
+            if (lane == 0) {
+                int k = ko, ps = passes, cap[2] = {cap0, cap1}, m = nh;
+                uint64_t bh = hash;
+                if (go_play_seq(t, board, gl, a, p, k, ps, bh, nullptr, cap) && t.superko) ph[m++] = go_hash(t, bh, p, k);
+                S.bh = bh; S.ko = k; S.passes = ps; S.cap[0] = cap[0]; S.cap[1] = cap[1]; S.nh = m;
+                S.res = ps >= 2 ? go_result_seq(t, board, gl, cap) : R_ONGOING;
+            }
+            __syncthreads();
+            hash = S.bh; ko = S.ko; passes = S.passes; cap0 = S.cap[0]; cap1 = S.cap[1]; nh = S.nh; res = S.res;
+            stones += a >= 0 ? 1 : 0;
+            __syncthreads();                      // S is read before the next ply rewrites it
+        } else {
+            // GomokuState::make_move, as k_apply
+            __syncthreads();                      // the judging reads of the board are over
+            if (lane == 0) board[a] = (uint8_t)p;
+            __syncthreads();
+            int r = R_ONGOING;
+            if (five_at_wave(board, t.bs, a, p, lane)) r = p == 1 ? R_WIN1 : R_WIN2;
+            else if (stones + 1 >= A) r = R_DRAW;
+            else if (rules && p == 2 && forbidden_mask_wave(t, board, lane, forb) == 0) r = R_DRAW;   // is_stalemate
+            if (i >= nm && r != R_ONGOING) {      // a random ply never ends the game: the stone comes off again
+                __syncthreads();
+                if (lane == 0) board[a] = 0;
+                __syncthreads();
+                break;
+            }
+            hash ^= t.zpiece[(size_t)(p - 1) * A + a] ^ t.zplayer[p - 1] ^ t.zplayer[2 - p];
+            stones += 1;
+            res = r;
+        }
+        for (int j = 5; j > 0; --j) h6[j] = h6[j - 1];
+        h6[0] = a;
+        p = 3 - p;
+        if (i >= nm) {
+            if (lane == 0 && o.picks) o.picks[(size_t)idx * o.rplies + nrand] = a;
+            ++nrand;
+        }
+    }
+    const int np = nm + nrand;                    // plies played
+    if (lane == 0) {
+        rep[0] = bad; rep[1] = why; rep[2] = bad < 0 && res == R_ONGOING; rep[3] = res; rep[4] = nrand;
+    }
+    if (dry || bad >= 0) return;
+    __syncthreads();
+    uint8_t* rb = t.rboard + (size_t)g * A;
+    for (int i = lane; i < A; i += 64) rb[i] = board[i];
+    GamePtrs nd = game_nodes(t.nd, (size_t)g * t.ncap);
+    long long* cnt = t.cnt + (size_t)g * AZ_NCNT;
+    if (lane < CNT_EVALS_TOTAL) cnt[lane] = 0;
+    if (lane == 0) {
+        for (int j = 0; j < 6; ++j) t.rhist[g * 6 + j] = h6[j];
+        t.rplayer[g] = p; t.rstones[g] = stones; t.rply[g] = np; t.rfresh[g] = np == 0;
+        t.rhash[g] = hash;
+        if (go) { t.rko[g] = ko; t.rpass[g] = passes; t.rnposh[g] = nh; t.rcap[2 * g] = cap0; t.rcap[2 * g + 1] = cap1; }
+        t.rnode[g] = 0; t.atop[g] = 1; t.active[g] = res == R_ONGOING; t.gresult[g] = res; t.ring_cur[g] = 0;
+        nd.N[0] = 0; nd.W[0] = 0.0f; nd.VL[0] = 0; nd.P[0] = 0.0f; nd.first[0] = -1; nd.act[0] = -1;
+        nd.cnt[0] = 0; nd.flag[0] = 0;
+        if (t.mt) {
+            // std::mt19937(seed + id) seeding, as k_new_games
+            uint32_t* st = t.mt + (size_t)g * 625;
+            st[0] = o.eval_seed + (uint32_t)sid;
             for (int i = 1; i < 624; ++i) st[i] = 1812433253u * (st[i - 1] ^ (st[i - 1] >> 30)) + (uint32_t)i;
             st[624] = 624;
         }

@@ -310,6 +310,53 @@ int az_search_release_masked(az_search* s, int threshold, int64_t* pruned, const
 /* az_search_new_games with each game's stream id for the evaluator / noise seeds given (default:
  * the slot index): id 0 makes a slot's game the one a single-game handle plays. */
 int az_search_new_games_ids(az_search* s, const int* games, const int* seed_ids, int n);
+/* Fresh games in the listed slots, each advanced by its own move sequence: moves[i*stride .. i*stride +
+ * n_moves[i]) (Go: -1 is the pass).  seed_ids may be null (the slot index).  One launch plays every
+ * sequence; afterwards the handle is as after az_search_new_games_ids on the same slots and ids followed by
+ * one az_search_apply per move -- every later search, selection, move, root readback, counter and
+ * evaluation-log entry is equal bit for bit.  The last move of a sequence may end the game: the slot is then
+ * inactive with that result.  n_moves[i] == 0 is az_search_new_games_ids.
+ * Every move is judged against the rules before anything is written.  AZ_ERR_ARG, with the handle exactly
+ * as it was and az_last_error() naming the entry, the ply and the reason: a slot index out of range,
+ * n_moves[i] < 0 or > stride, an action out of range, an occupied cell, a cell forbidden to Black under
+ * Renju / Omok, Go suicide, the ko point, a superko repeat, a move after the game has ended.
+ * AZ_ERR_CAPACITY (nothing changed): more stone moves than the device's position history holds (Go with
+ * superko).  az_search_apply judges a Go move the same way (AZ_ERR_ARG, nothing moved). */
+int az_search_new_games_moves(az_search* s, const int* games, const int* seed_ids, int n, const int* moves,
+                              const int* n_moves, int stride);
+
+/* Openings of the games the drivers start on the handle (az_selfplay_step restarts, az_selfplay_run, the arena
+ * through az_arena_search): game `id` (its stream id) begins with opening id % n_openings of the book, then
+ * plays up to random_plies further plies drawn on the device, and only then is searched -- so a game's record
+ * does not depend on n_games.  Plain az_search_new_games* calls stay empty-board starts.
+ * Random ply j (the game's real ply number) of game id: Philox4x32-10 with key (seed lo, seed hi) and counter
+ * (id, j, 0, 0); the legal moves of the side to move in ascending action order (Gomoku: the empty cells less
+ * the forbidden ones; Go: the legal points, superko included, without the pass); the pick is
+ * legal[(out0 * n_legal) >> 32].  A pick that would end the game (a five, a full board, Black left without a
+ * legal cell) is not played and the opening stops there, as at an empty list: random plies never end a game.
+ * The book is copied (host and device) and every opening is judged as az_search_new_games_moves judges a
+ * sequence: an illegal opening or one that ends the game is AZ_ERR_ARG naming it, random_plies < 0 is
+ * AZ_ERR_ARG, n_openings == 0 with random_plies > 0 is valid (random plies from the empty board), and a
+ * refused call leaves the openings in force as they were.  cfg null (or no openings and no random plies): none.
+ * The openings survive az_search_set_params, az_search_set_options, az_search_set_net and az_search_clear_tt.
+ * Records (az_selfplay_run, az_arena_run): a game's move list begins with its opening plies, each with the
+ * action, value 0, n_children 0, null arrays and thinking_time_ms 0, so it replays from the empty board;
+ * moves_done, the progress callback's total and az_arena_summary.moves count searched moves only, max_moves
+ * counts real plies, and nothing is staged in an attached replay buffer for an opening ply.  Arena: both trees
+ * of a table are opened with the same sequence; with swap_colors the opening and the random stream are those
+ * of game_id / 2, so ids 2k and 2k + 1 play one opening with the colours swapped; mover[i] of an opening ply
+ * is the net that owns that colour. */
+typedef struct az_openings_cfg {
+    const int* moves;     /* book, [n_openings][stride] */
+    const int* n_moves;
+    int n_openings;
+    int stride;
+    int random_plies;     /* played after the book's plies; 0: none */
+    uint64_t seed;        /* Philox key of the random plies */
+} az_openings_cfg;
+int az_search_set_openings(az_search* s, const az_openings_cfg* cfg);  /* null: none */
+/* The openings in force: book size (0 with none), random plies, seed; any pointer may be null. */
+int az_search_openings(az_search* s, int* n_openings, int* random_plies, uint64_t* seed);
 /* ParallelMCTS::selectAction(isTraining, T) of one game (parallel_mcts.cpp:987-1047).
  * batch_inference != 0 (MCTSConfig::useBatchInference, forced by setDeterministicMode and
  * SelfPlayManager): the deterministic rules of az_search_select.  Otherwise draws on the game's

@@ -69,6 +69,9 @@ def main():
     ap.add_argument("--steps", type=int, default=1, help="SGD steps per round")
     ap.add_argument("--lr", type=float, default=0.02)
     ap.add_argument("--seed", type=int, default=0)
+    ap.add_argument("--random-opening-plies", type=int, default=0,
+                    help="every game begins with this many random legal plies drawn on the device (each round under a "
+                         "seed of its own); the replay buffer holds the searched positions only")
     args = ap.parse_args()
 
     eng = az_amd.Engine(0)
@@ -93,6 +96,8 @@ def main():
     log = []
     for rnd in range(args.rounds):
         t0 = time.perf_counter()
+        if args.random_opening_plies:   # a round numbers its games from 0 again: another seed, other openings
+            mgr.setOpenings(None, args.random_opening_plies, seed=(args.seed << 32) + rnd)
         mgr.generateGames(args.games, max_moves=args.max_moves)
         t1 = time.perf_counter()
         model.train()
