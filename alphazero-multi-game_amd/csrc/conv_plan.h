@@ -35,6 +35,10 @@
 //                           chunk reloads itself, the residual join reads global  main loop measured 0.6 % slower and was removed; a
 //                           memory)                                               cross-row fragment prefetch and a mid-row barrier
 //                                                                                 1.5-2 % slower)
+//  CONV_F_V7_OLD_EPILOGUE 0x8000 the row-streamed loop ends in the shared tile    read by the kernel.  B = 2048, fp16, lean against
+//                           epilogue (per-element pointer tests, 64-bit store     shared in one process: 0.4244 vs 0.4592 ms per
+//                           addresses), not its own lean one                      launch, reversed 0.4249 vs 0.4618 (-7.6 / -8.0 %,
+//                                                                                 spread 0.0115; profiles/r10_v7_epilogue_ab.txt)
 //  CONV_F_V7_TM     0x70000 force v7's DENSE tile rows: 1 = 256, 2 = 128,         conv_v7_tm below
 //                           3 = 64, 4 = 192
 //  CONV_F_V7_RING3  0x80000 3-slot weight ring for tiles of at most 128 rows      conv_v7_ring below
@@ -46,7 +50,7 @@
 enum : int {
     CONV_F_V6_AT_15 = 0x4, CONV_F_DENSE_15 = 0x8, CONV_F_NO_V7 = 0x100, CONV_F_V7_ONLY_15 = 0x200, CONV_F_V7_PAD_15 = 0x400,
     CONV_F_V7_ANY_BATCH = 0x800, CONV_F_V6_SMALL = 0x1000, CONV_F_V7_PER_TAP = 0x2000, CONV_F_V7_OLD_TAIL = 0x4000,
-    CONV_F_V7_TM = 0x70000, CONV_F_V7_TM_SHIFT = 16, CONV_F_V7_RING3 = 0x80000, CONV_F_KEEP_POOL = 0x400000,
+    CONV_F_V7_OLD_EPILOGUE = 0x8000, CONV_F_V7_TM = 0x70000, CONV_F_V7_TM_SHIFT = 16, CONV_F_V7_RING3 = 0x80000, CONV_F_KEEP_POOL = 0x400000,
     CONV_F_FC_F32 = 0x08000000, CONV_F_V7X3 = 0x10000000, CONV_F_V9_TAP_BARRIER = 0x20000000,
     CONV_F_V9_KEEP_FRAG = 0x40000000,
     CONV_F_DEFAULT = CONV_F_V6_AT_15 | CONV_F_V7_ONLY_15   // 0x204

@@ -27,6 +27,8 @@
 //    40 KB into which a 2nd conv's residual tile is fetched by LDS-DMA during the main loop (the last
 //    five of its 15 fragment rows go into the halo buffer the peeled last chunk leaves idle), so the
 //    epilogue's join reads LDS and the residual's HBM traffic is spread over the tile's MFMA time.
+//    It ends in an epilogue of its own (epilogue_rows: the residual / remainder tests decided once per
+//    wave, buffer stores from one base per wave and plane; conv flag 0x8000 keeps the shared one).
 //
 // Tile geometry (as v6): 15x15 boards use the padded grid (outputs on a 15x17 grid, one board per
 // 256-row tile, 225 of 256 rows live) or DENSE tiles; every other board uses DENSE tiles (256
@@ -180,6 +182,27 @@ __device__ __forceinline__ void wait_vm(int n) {      // s_waitcnt vmcnt(n), n w
         case 11: asm volatile("s_waitcnt vmcnt(11)" ::: "memory"); break;
         default: asm volatile("s_waitcnt vmcnt(12)" ::: "memory"); break;
     }
+}
+
+// The row-streamed epilogue's output stores: a buffer store through a wave-uniform resource `rs`
+// (four SGPRs) at the lane's byte offset `vo` + the scalar offset `so` + the immediate OFF (< 4096).
+// asm volatile with a memory clobber, as the shared epilogue's global stores: the stores stay in
+// program order, which is what keeps the rows' LDS reads and conversions from being hoisted in one go.
+typedef uint32_t u32x4_t __attribute__((ext_vector_type(4)));
+__device__ __forceinline__ u32x4_t store_rsrc(const void* base, uint32_t bytes) {   // base wave-uniform
+    const uint64_t a = (uint64_t)(uintptr_t)base;
+    return u32x4_t{(uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)a),
+                   (uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)(a >> 32)) & 0xffffu, bytes, 0x00020000u};
+}
+template <int OFF>
+__device__ __forceinline__ void bst_b64(u32x2_t v, uint32_t vo, u32x4_t rs, int so) {
+    static_assert(OFF >= 0 && OFF < 4096, "buffer immediate");
+    asm volatile("buffer_store_dwordx2 %0, %1, %2, %3 offen offset:%4" AZ_V7_ST ::"v"(v), "v"(vo), "s"(rs), "s"(so), "i"(OFF) : "memory");
+}
+template <int OFF>
+__device__ __forceinline__ void bst_b32(uint32_t v, uint32_t vo, u32x4_t rs, int so) {
+    static_assert(OFF >= 0 && OFF < 4096, "buffer immediate");
+    asm volatile("buffer_store_dword %0, %1, %2, %3 offen offset:%4" AZ_V7_ST ::"v"(v), "v"(vo), "s"(rs), "s"(so), "i"(OFF) : "memory");
 }
 
 template <int I, int N, typename Fn>
@@ -548,6 +571,86 @@ __global__ __launch_bounds__(256, RG == 3 ? 3 : 2) void conv3x3_v7(ConvBf16Args 
                 h = *reinterpret_cast<const u32x2_t*>(src);
                 q = QV[i][j];
             };
+            // The row-streamed path's own epilogue (the default; conv flag 0x8000 keeps the shared one
+            // above, which tests p.Rhi / p.Cq per element and rebuilds a 64-bit address per store: about
+            // 3 100 instructions per wave between the first and the last store against 1 780 here on a
+            // 2nd conv, 263 on a first conv -- DESIGN.md section 5.3, "Round 10").  Same values, same
+            // arithmetic, same stored bytes; what differs is the bookkeeping around them:
+            //  * RES (a residual tile is on chip) and REM (the int8 remainder plane is written) are
+            //    compile-time facts, one copy per combination net_forward launches: a first conv
+            //    (no, no), a 2nd conv (yes, yes), a 2nd conv of a net without residual (no, yes);
+            //  * one buffer resource per output plane whose base is the wave's own tile -- board `tile`,
+            //    channel groups (n0 + 32 wave) / 8 .. + 3 -- and whose range is exactly that tile (4 x HW
+            //    x 16 B; half in the int8 plane): a store's offset is the lane's part (group pair, pixel
+            //    column, channel half), the operand's 2 HW x 16 B in a scalar and the fragment row's
+            //    HB x 16 B as an immediate.  No 64-bit arithmetic per store, and no plane size limit;
+            //  * the dead 16th grid column is one execution mask around the whole body (its accumulators
+            //    stay out of the range guard, as in the shared epilogue);
+            //  * rows go in bursts of three behind scheduling fences, so the live set stays the
+            //    accumulators, the remainders and one burst's operands.
+            auto epilogue_rows = [&](auto rc, auto qc) {
+                constexpr bool RES = decltype(rc)::value, REM = decltype(qc)::value;
+                constexpr int EB = 3;
+                static_assert(NF % EB == 0 && (NF - 1) * HB * 16 < 4096, "bursts, store immediates");
+                int* const ovf = p.ovf;
+                const size_t ebase = ((size_t)tile * GO + (n0 + wave * 32) / 8) * HW * 8;
+                const u32x4_t rsH = store_rsrc(p.Chi + ebase, 4 * HW * 16);
+                const u32x4_t rsQ = REM ? store_rsrc(p.Cq + ebase, 4 * HW * 8) : u32x4_t{};
+                const uint32_t voQ = (uint32_t)(((lg >> 1) * HW + l16) * 8 + (lg & 1) * 4), voH = 2 * voQ;
+                const uint32_t lsrc = (uint32_t)((lg >> 1) * 256 + l16 * 16 + (lg & 1) * 8);
+                float vmax = 0.0f;                        // fp16: the largest live output (the range guard)
+                if (l16 < HB) {
+                    static_for<0, NF / EB>([&](auto bc) {
+                        constexpr int i0 = decltype(bc)::value * EB;
+                        u32x2_t hv[EB][2];
+                        if constexpr (RES) {
+                            static_for<0, EB>([&](auto ic) {
+                                constexpr int ii = decltype(ic)::value, i = i0 + ii;
+                                const uint8_t* src = (i < RR0 ? r_lo + i * R_ROW : r_hi + (i - RR0) * R_ROW) + lsrc;
+#pragma unroll
+                                for (int j = 0; j < 2; ++j) hv[ii][j] = *reinterpret_cast<const u32x2_t*>(src + j * 512);
+                            });
+                        }
+#ifdef AZ_V7_STAMPS
+                        if constexpr (i0 == 0) {          // the first burst's residual operands are in registers
+                            asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");
+                            V7_STAMP(3);
+                        }
+#endif
+                        static_for<0, 2 * EB>([&](auto sc) {
+                            constexpr int ii = decltype(sc)::value / 2, j = decltype(sc)::value % 2, i = i0 + ii;
+                            float o[4] = {acc[i][j][0], acc[i][j][1], acc[i][j][2], acc[i][j][3]};
+                            if constexpr (RES) {
+                                uint16_t hh[4];
+                                int8_t qq[4];
+                                __builtin_memcpy(hh, &hv[ii][j], 8);
+                                __builtin_memcpy(qq, &QV[i][j], 4);
+#pragma unroll
+                                for (int k = 0; k < 4; ++k) o[k] += H::join(hh[k], qq[k]);
+                            }
+                            uint16_t oh[4];
+                            int8_t oq[4];
+#pragma unroll
+                            for (int k = 0; k < 4; ++k) {
+                                o[k] = __builtin_amdgcn_fmed3f(o[k], 0.0f, 3.0e38f);   // ReLU
+                                if constexpr (MODE == 2) vmax = __builtin_fmaxf(vmax, o[k]);
+                                if constexpr (REM) H::split(o[k], oh[k], oq[k]);
+                                else oh[k] = H::from_f(o[k]);
+                            }
+                            u32x2_t hs;
+                            __builtin_memcpy(&hs, oh, 8);
+                            bst_b64<i * HB * 16>(hs, voH, rsH, j * (2 * HW * 16));
+                            if constexpr (REM) {
+                                uint32_t qs;
+                                __builtin_memcpy(&qs, oq, 4);
+                                bst_b32<i * HB * 8>(qs, voQ, rsQ, j * (2 * HW * 8));
+                            }
+                        });
+                        __builtin_amdgcn_sched_barrier(0);
+                    });
+                    if (MODE == 2 && !(vmax <= 65504.0f) && ovf) atomicOr(ovf, 1);   // fp16 overflow: the engine fails the forward
+                }
+            };
 
             // one chunk; lastc: the peeled last chunk
             auto chunk = [&](const int c, auto lastc) {
@@ -647,8 +750,14 @@ __global__ __launch_bounds__(256, RG == 3 ? 3 : 2) void conv3x3_v7(ConvBf16Args 
             lgkm1<0>(F[1]);
             lgkm1<0>(F[2]);
             asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");
+            // wave-uniform: the lean epilogue by what the launch has (a residual without a remainder
+            // plane is launched by nobody and takes the shared epilogue, as flags 0x4000 / 0x8000 do)
+            const bool rem = p.Cq != nullptr;
             if (tail_old) epilogue(acc, 0, n0 + wave * 32 + 4 * lg, res_mem);
-            else epilogue(acc, 0, n0 + wave * 32 + 4 * lg, res_lds);
+            else if ((p.flags & CONV_F_V7_OLD_EPILOGUE) || (resid && !rem)) epilogue(acc, 0, n0 + wave * 32 + 4 * lg, res_lds);
+            else if (resid) epilogue_rows(std::true_type{}, std::true_type{});
+            else if (rem) epilogue_rows(std::false_type{}, std::true_type{});
+            else epilogue_rows(std::false_type{}, std::false_type{});
 #ifdef AZ_V7_STAMPS
             V7_STAMP(4);
             asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
