@@ -144,16 +144,6 @@ int gather_host(az_replay* r, const int64_t* idx, const int* sym, int n, float* 
     return rc;
 }
 
-// Philox4x32-10 (Salmon et al., "Parallel random numbers: as easy as 1, 2, 3", SC'11)
-void philox4x32_10(uint32_t c[4], uint32_t k0, uint32_t k1) {
-    for (int round = 0; round < 10; ++round) {
-        const uint64_t p0 = (uint64_t)0xD2511F53u * c[0], p1 = (uint64_t)0xCD9E8D57u * c[2];
-        const uint32_t n0 = (uint32_t)(p1 >> 32) ^ c[1] ^ k0, n2 = (uint32_t)(p0 >> 32) ^ c[3] ^ k1;
-        c[0] = n0; c[1] = (uint32_t)p1; c[2] = n2; c[3] = (uint32_t)p0;
-        k0 += 0x9E3779B9u; k1 += 0xBB67AE85u;
-    }
-}
-
 // the slot ids and empty staging of the owner's slots `games` (null: all); s->mu and r->mu held
 int reset_slots(az_replay* r, az_search* s, const int* games, int n) {
     hipStream_t st = r->e->stream;

@@ -440,6 +440,21 @@ int search_run(az_search* s) {
     return r;
 }
 
+namespace {
+// The host mirrors of slot g after a game with stream id `id` has started in it with `plies` plies played
+// (s->hist[g] is the caller's): as a fresh game and `plies` search_apply_dev leave them -- stones counts a
+// Go pass too.
+void slot_started(az_search* s, int g, int id, int plies, int active) {
+    s->stones[g] = plies; s->active[g] = active; s->fresh[g] = plies == 0; s->ply[g] = plies;
+    if (plies) s->used = true;                           // moves have been made (az_search_set_gomoku_rules comes before)
+    s->roots_ready = false;                              // a fresh root: unexpanded
+    s->slot_id[g] = id;
+    s->sp_next_id = std::max(s->sp_next_id, id + 1);
+    pf_drop(s, g);
+    s->rng[g].seed(s->c.noise_seed + (uint32_t)(s->c.noise_seed_stride * id));
+}
+}  // namespace
+
 // (Re)start the listed slots with fresh games.  seed_ids (optional) give each game its own
 // stream id for the evaluator / noise seeds (default: the slot index), so a game's record
 // does not depend on which slot plays it.
@@ -457,15 +472,8 @@ int search_new_games(az_search* s, const int* games, int n, const int* seed_ids)
     HIPCHK(hipGetLastError());
     HIPCHK(hipStreamSynchronize(st));
     for (int i = 0; i < n; ++i) {
-        const int g = games[i];
-        s->stones[g] = 0; s->active[g] = 1; s->fresh[g] = 1; s->ply[g] = 0;
-        s->hist[g].clear();
-        s->roots_ready = false;                          // a fresh root: unexpanded
-        const int id = seed_ids ? seed_ids[i] : g;
-        s->slot_id[g] = id;
-        s->sp_next_id = std::max(s->sp_next_id, id + 1);
-        pf_drop(s, g);
-        s->rng[g].seed(s->c.noise_seed + (uint32_t)(s->c.noise_seed_stride * id));
+        s->hist[games[i]].clear();
+        slot_started(s, games[i], seed_ids ? seed_ids[i] : games[i], 0, 1);
     }
     if (s->replay) return replay_discard(s, games, n);   // a new game in the slot: its staged positions go
     return 0;
@@ -554,16 +562,7 @@ int open_games_run(az_search* s, const OpenJob& j, bool validate, std::vector<st
         h.clear();
         if (nm) h.assign(j.moves + (size_t)seq * j.stride, j.moves + (size_t)seq * j.stride + nm);
         h.insert(h.end(), picks.begin() + (size_t)i * j.rplies, picks.begin() + (size_t)i * j.rplies + nr);
-        const int np = nm + nr;
-        // the mirrors as search_new_games and np search_apply_dev leave them (stones counts a Go pass too)
-        s->stones[g] = np; s->active[g] = rep[AZ_OPEN_REP * i + 2]; s->fresh[g] = np == 0; s->ply[g] = np;
-        if (np) s->used = true;                          // moves have been made (az_search_set_gomoku_rules comes before)
-        s->roots_ready = false;
-        const int id = j.seed_ids ? j.seed_ids[i] : g;
-        s->slot_id[g] = id;
-        s->sp_next_id = std::max(s->sp_next_id, id + 1);
-        pf_drop(s, g);
-        s->rng[g].seed(s->c.noise_seed + (uint32_t)(s->c.noise_seed_stride * id));
+        slot_started(s, g, j.seed_ids ? j.seed_ids[i] : g, nm + nr, rep[AZ_OPEN_REP * i + 2]);
         if (played) (*played)[i] = h;
     }
     if (s->replay) return replay_discard(s, j.games, n);   // a new game in the slot: its staged positions go
@@ -1196,21 +1195,11 @@ int az_search_apply(az_search* s, const int* actions, int* terminal, int* result
         if (actions[g] >= A || (s->t.game == GAME_GO && actions[g] < AZ_ACTION_NONE))
             return az_fail(AZ_ERR_ARG, "action %d out of range for game %d", actions[g], g);
     HIPCHK(hipMemcpyAsync(s->d_actions, actions, G * 4, hipMemcpyHostToDevice, s->e->stream));
-    if (tree_has_rules(s->t)) {
-        // GomokuState::make_move throws on a cell the rules forbid Black: refused before anything moves
+    if (s->t.game == GAME_GO || tree_has_rules(s->t)) {
+        // GoState::makeMove / GomokuState::make_move throw on a move that is not legal: refused before anything
+        // moves.  (Plain Gomoku has only the occupied cell to refuse and is not judged here: no launch, no wait.)
         std::vector<int> bad(G);
-        hipLaunchKernelGGL(k_forbidden_moves, dim3(G), dim3(64), 0, s->e->stream, s->t, s->d_actions, s->d_nch);
-        HIPCHK(hipGetLastError());
-        HIPCHK(hipMemcpyAsync(bad.data(), s->d_nch, G * 4, hipMemcpyDeviceToHost, s->e->stream));
-        HIPCHK(hipStreamSynchronize(s->e->stream));
-        for (int g = 0; g < G; ++g)
-            if (bad[g]) return az_fail(AZ_ERR_ARG, "action %d of game %d is forbidden to Black under the %s rules", actions[g], g,
-                                       s->t.renju ? "Renju" : "Omok");
-    }
-    if (s->t.game == GAME_GO) {
-        // GoState::makeMove throws on a move that is not legal: refused before anything moves
-        std::vector<int> bad(G);
-        hipLaunchKernelGGL(k_go_illegal_moves, dim3(G), dim3(64), 0, s->e->stream, s->t, s->d_actions, s->d_nch);
+        hipLaunchKernelGGL(k_illegal_moves, dim3(G), dim3(64), 0, s->e->stream, s->t, s->d_actions, s->d_nch);
         HIPCHK(hipGetLastError());
         HIPCHK(hipMemcpyAsync(bad.data(), s->d_nch, G * 4, hipMemcpyDeviceToHost, s->e->stream));
         HIPCHK(hipStreamSynchronize(s->e->stream));

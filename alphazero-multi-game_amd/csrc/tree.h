@@ -29,7 +29,7 @@ enum { ERR_NODES = 1, ERR_PATH = 2, ERR_RING = 4, ERR_BATCH = 8, ERR_HIST = 16, 
 // MCTSNodeSelection (include/alphazero/mcts/parallel_mcts.h:26-31); RAVE plays PUCT (selectChildRave)
 enum { SEL_UCB = 0, SEL_PUCT = 1, SEL_PROGRESSIVE_BIAS = 2, SEL_RAVE = 3 };
 enum { GAME_GOMOKU = 0, GAME_GO = 1 };
-// why k_open_games / k_go_illegal_moves refuse a move (0: legal)
+// why the move judge (move_reason: k_open_games, k_illegal_moves) refuses a move (0: legal)
 enum { AZ_OPEN_RANGE = 1, AZ_OPEN_OCCUPIED = 2, AZ_OPEN_FORBIDDEN = 3, AZ_OPEN_SUICIDE = 4, AZ_OPEN_KO = 5,
        AZ_OPEN_SUPERKO = 6, AZ_OPEN_ENDED = 7 };
 
@@ -63,7 +63,7 @@ struct TreeDev {
     float komi; int chinese; int superko;
     // GomokuState(bs, use_renju, use_omok): fixed per game sequence and uniform over the grid, read only by the
     // kernels' RULES instantiations (launched when tree_has_rules()) and by the per-move kernels.  The hash
-    // keys "renju"[1] / "omok"[1] are in zconst (Gomoku: XORed into the fresh root's hash by k_new_games)
+    // keys "renju"[1] / "omok"[1] are in zconst (Gomoku: XORed into the start position's hash, root_empty)
     int renju, omok;
     int pad3 = 0;
     int* gresult;                // [G] GameResult of the root state
@@ -171,6 +171,19 @@ inline int replay_sym_cell(int bs, int sym, int cell) {
     if (sym & 4) c = n - c;
     for (int k = sym & 3; k > 0; --k) { const int t = r; r = c; c = n - t; }
     return r * bs + c;
+}
+// Philox4x32-10 (Salmon et al., "Parallel random numbers: as easy as 1, 2, 3", SC'11): the replay buffer's
+// sample plan (host) and the openings' random plies (k_open_games) draw from it
+#if defined(__HIPCC__)
+__host__ __device__
+#endif
+inline void philox4x32_10(uint32_t c[4], uint32_t k0, uint32_t k1) {
+    for (int round = 0; round < 10; ++round) {
+        const uint64_t p0 = (uint64_t)0xD2511F53u * c[0], p1 = (uint64_t)0xCD9E8D57u * c[2];
+        const uint32_t n0 = (uint32_t)(p1 >> 32) ^ c[1] ^ k0, n2 = (uint32_t)(p0 >> 32) ^ c[3] ^ k1;
+        c[0] = n0; c[1] = (uint32_t)p1; c[2] = n2; c[3] = (uint32_t)p0;
+        k0 += 0x9E3779B9u; k1 += 0xBB67AE85u;
+    }
 }
 
 // Training-example extraction (Dataset::extractExamples + augmentExample).

@@ -23,15 +23,14 @@ __global__ void k_scan_nets(const TreeDev* __restrict__ tp, const uint8_t* __res
 __global__ void k_select_action(const TreeDev* __restrict__ tp, int training, float temperature, const float* temps, int* actions, float* values, float* probs,
                                 int* child_actions, int* nchild);
 __global__ void k_apply(TreeDev t, const int* actions, int* terminal, int* result, int* rexp);
-// Renju / Omok: bad[g] = 1 when actions[g] is a cell the rules forbid game g's side to move
-__global__ void k_forbidden_moves(TreeDev t, const int* actions, int* bad);
+// bad[g] = the AZ_OPEN_* reason the rules refuse actions[g] on game g's root position for (0: legal, a pass, no
+// move, a game not playing); for a Go handle or tree_has_rules()
+__global__ void k_illegal_moves(TreeDev t, const int* actions, int* bad);
 __global__ void k_compact(TreeDev t, Nodes dst, int* src_of);
 __global__ void k_leaf_moves(TreeDev t, int* moves, int* len);
 __global__ void k_prune(TreeDev t, Nodes dst, int* src_of, int thr_all, const int* thr_g, long long* pruned);
 __global__ void k_noise(TreeDev t, const float* noise, const uint8_t* mask, float eps);
 __global__ void k_new_games(TreeDev t, const int* games, const int* seed_ids, int n, uint32_t eval_seed);
-// Go: bad[g] = the AZ_OPEN_* reason the rules refuse actions[g] of game g for (0: legal, a pass, no move)
-__global__ void k_go_illegal_moves(TreeDev t, const int* actions, int* bad);
 // openings (OpenDev, tree.h): fresh games in the listed slots, each advanced by a move sequence with every move
 // judged against the rules, then by random plies drawn on the device; dry: nothing of the slots is written
 __global__ void k_open_games(TreeDev t, OpenDev o);

@@ -159,24 +159,8 @@ __device__ __forceinline__ float convert_value(int result, int player) {
     return 0.0f;
 }
 
-// count_direction / check_line_for_five (gomoku_rules.cpp:62-115): run through cell a.
-__device__ int five_at(const uint8_t* board, int bs, int a, int p) {
-    int x0 = a / bs, y0 = a % bs;
-    const int D[4][2] = {{0, 1}, {1, 0}, {1, 1}, {1, -1}};
-    for (int d = 0; d < 4; ++d) {
-        int len = -1;
-        for (int s = -1; s <= 1; s += 2) {
-            int x = x0, y = y0;
-            while (x >= 0 && x < bs && y >= 0 && y < bs && board[x * bs + y] == p) {
-                ++len; x += s * D[d][0]; y += s * D[d][1];
-            }
-        }
-        if (p == 1 ? len == 5 : len >= 5) return 1;
-    }
-    return 0;
-}
-
-// five_at over the wave: lanes 0..7 walk the 8 rays (4 directions x 2 sides) at once, each capped
+// count_direction / check_line_for_five (gomoku_rules.cpp:62-115): does the run of p's stones through cell a
+// make five?  Lanes 0..7 walk the 8 rays (4 directions x 2 sides) at once, each capped
 // at 5 cells (1 + min(L,5) + min(R,5) is 5 exactly when the run is 5, and >= 5 exactly when it is).
 // Every lane of the wave must call it (wave-uniform arguments).
 __device__ int five_at_wave(const uint8_t* board, int bs, int a, int p, int lane) {
@@ -298,6 +282,12 @@ __device__ uint32_t mt_next(uint32_t* st) {
     z ^= (z >> 18);
     return z;
 }
+// std::mt19937(seed) seeding (libstdc++ mersenne_twister_engine::seed)
+__device__ void mt_seed(uint32_t* st, uint32_t seed) {
+    st[0] = seed;
+    for (int i = 1; i < 624; ++i) st[i] = 1812433253u * (st[i - 1] ^ (st[i - 1] >> 30)) + (uint32_t)i;
+    st[624] = 624;
+}
 // uniform_real_distribution<float>(a, b) over generate_canonical<float, 24>
 __device__ float mt_uniform(uint32_t* st, float a, float b) {
     float c = (float)mt_next(st) / 4294967296.0f;
@@ -313,6 +303,11 @@ __device__ __forceinline__ GamePtrs game_nodes(const Nodes& nd, size_t base) {
     p.N = nd.N + base; p.W = nd.W + base; p.VL = nd.VL + base; p.P = nd.P + base;
     p.first = nd.first + base; p.act = nd.act + base; p.cnt = nd.cnt + base; p.flag = nd.flag + base;
     return p;
+}
+// node i as a new node: no visits, no children, no move
+__device__ __forceinline__ void node_clear(const GamePtrs& nd, int i) {
+    nd.N[i] = 0; nd.W[i] = 0.0f; nd.VL[i] = 0; nd.P[i] = 0.0f;
+    nd.first[i] = -1; nd.act[i] = -1; nd.cnt[i] = 0; nd.flag[i] = 0;
 }
 
 // Leaf state = root state + path moves: k_select and k_expand_backup build the Gomoku leaf board
@@ -1752,140 +1747,6 @@ __global__ __launch_bounds__(64) void k_select_action(const TreeDev* __restrict_
     }
 }
 
-// updateWithMove's subtree reuse (parallel_mcts.cpp:1065-1108): the child that played `a`
-// becomes the root, else a fresh root node.  Lane 0.
-// returns the flag of the new root (0 for a fresh node)
-__device__ uint8_t reuse_child(const TreeDev& t, int g, const GamePtrs& nd, int a) {
-    const int root = t.rnode[g];
-    const int fc = nd.first[root], nc = nd.cnt[root];
-    int child = -1;
-    for (int i = 0; i < nc; ++i) if (nd.act[fc + i] == a) { child = fc + i; break; }
-    if (child < 0) {
-        child = t.atop[g];
-        if (child + 1 > t.ncap) { atomicOr(t.err, ERR_NODES); child = 0; }
-        else t.atop[g] = child + 1;
-        nd.N[child] = 0; nd.W[child] = 0.0f; nd.VL[child] = 0; nd.P[child] = 0.0f;
-        nd.first[child] = -1; nd.act[child] = -1; nd.cnt[child] = 0; nd.flag[child] = 0;
-        t.rnode[g] = child;
-        return 0;
-    }
-    t.rnode[g] = child;
-    return nd.flag[child];
-}
-
-// K5: makeMove + updateWithMove; terminal test of the new root (game loop condition).
-// rexp[g] (optional): 1 when the game's root after the move needs no root expansion (expanded or
-// terminal, or the game is not playing) -- the host then skips the no-op root steps
-__global__ __launch_bounds__(64) void k_apply(TreeDev t, const int* actions, int* terminal, int* result, int* rexp) {
-    const int g = blockIdx.x;
-    const int lane = threadIdx.x;
-    __shared__ uint8_t board[AZ_MAXA];
-    __shared__ GoLds gl;
-    if (g >= t.G) return;
-    const int a = actions[g];
-    const int A = t.A;
-    const bool go = t.game == GAME_GO;
-    if (!t.active[g] || a < (go ? -1 : 0) || a >= A) {          // Go: -1 is the pass
-        if (lane == 0) {
-            terminal[g] = t.active[g] ? 0 : 1; result[g] = t.gresult[g];
-            if (rexp) rexp[g] = t.active[g] ? ((game_nodes(t.nd, (size_t)g * t.ncap).flag[t.rnode[g]] & (FL_EXPANDED | FL_TERMINAL)) != 0) : 1;
-        }
-        return;
-    }
-    GamePtrs nd = game_nodes(t.nd, (size_t)g * t.ncap);
-    uint8_t* rb = t.rboard + (size_t)g * A;
-    const int p = t.rplayer[g];
-    for (int i = lane; i < A; i += 64) board[i] = rb[i];
-    __syncthreads();
-    if (go) {
-        // GoState::makeMove (go_state.cpp:192-257)
-        go_clear_marks(gl, A, lane);
-        if (lane == 0) {
-            int pp = p, k = t.rko[g], ps = t.rpass[g];
-            uint64_t bh = t.rhash[g];
-            int* cap = t.rcap + 2 * g;
-            if (go_play_seq(t, board, gl, a, pp, k, ps, bh, nullptr, cap) && t.superko) {   // simple ko keeps no history
-                const int n = t.rnposh[g];
-                if (n >= t.hmax) atomicOr(t.err, ERR_HIST);
-                else { t.rposh[(size_t)g * t.hmax + n] = go_hash(t, bh, pp, k); t.rnposh[g] = n + 1; }
-            }
-            t.rhash[g] = bh; t.rko[g] = k; t.rpass[g] = ps; t.rplayer[g] = 3 - p;
-            int* h = t.rhist + g * 6;
-            for (int i = 5; i > 0; --i) h[i] = h[i - 1];
-            h[0] = a;
-            t.rstones[g] += a >= 0 ? 1 : 0;
-            t.rply[g] += 1;
-            t.rfresh[g] = 0;
-            const int res = ps >= 2 ? go_result_seq(t, board, gl, cap) : R_ONGOING;
-            t.gresult[g] = res;
-            if (res != R_ONGOING) t.active[g] = 0;
-            terminal[g] = res != R_ONGOING;
-            result[g] = res;
-            const uint8_t fl = reuse_child(t, g, nd, a);
-            if (rexp) rexp[g] = res != R_ONGOING || (fl & (FL_EXPANDED | FL_TERMINAL)) != 0;
-        }
-        __syncthreads();
-        for (int i = lane; i < A; i += 64) rb[i] = board[i];
-        return;
-    }
-    __shared__ int s_res;
-    if (lane == 0) {
-        board[a] = (uint8_t)p;
-        rb[a] = (uint8_t)p;
-        const int np = 3 - p;
-        t.rhash[g] = t.rhash[g] ^ t.zpiece[(size_t)(p - 1) * A + a] ^ t.zplayer[p - 1] ^ t.zplayer[np - 1];
-        int* h = t.rhist + g * 6;
-        for (int i = 5; i > 0; --i) h[i] = h[i - 1];
-        h[0] = a;
-        t.rplayer[g] = np;
-        const int stones = t.rstones[g] + 1;
-        t.rstones[g] = stones;
-        t.rply[g] += 1;
-        t.rfresh[g] = 0;
-        int res = R_ONGOING;
-        if (five_at(board, t.bs, a, p)) res = p == 1 ? R_WIN1 : R_WIN2;
-        else if (stones >= A) res = R_DRAW;
-        s_res = res;
-    }
-    if (t.renju || t.omok) {
-        // Renju / Omok: Black to move with every empty cell forbidden is a DRAW (is_stalemate, gomoku_state.cpp:506-521)
-        __syncthreads();
-        if (s_res == R_ONGOING && p == 2 && forbidden_mask_wave(t, board, lane, t.gforb + (size_t)g * AZ_FORB_WORDS) == 0 &&
-            lane == 0)
-            s_res = R_DRAW;
-    }
-    if (lane == 0) {
-        const int res = s_res;
-        t.gresult[g] = res;
-        if (res != R_ONGOING) t.active[g] = 0;
-        terminal[g] = res != R_ONGOING;
-        result[g] = res;
-        const uint8_t fl = reuse_child(t, g, nd, a);
-        if (rexp) rexp[g] = res != R_ONGOING || (fl & (FL_EXPANDED | FL_TERMINAL)) != 0;
-    }
-}
-
-// Renju / Omok: the moves az_search_apply is about to commit, against the rules -- bad[g] = 1 when
-// actions[g] is an empty cell the rules forbid game g's side to move (make_move throws there,
-// gomoku_state.cpp:697-703).  One wave per game; launched only on a handle with rules.
-__global__ __launch_bounds__(64) void k_forbidden_moves(TreeDev t, const int* actions, int* bad) {
-    const int g = blockIdx.x;
-    const int lane = threadIdx.x;
-    __shared__ uint8_t board[AZ_MAXA];
-    if (g >= t.G) return;
-    const int a = actions[g], A = t.A;
-    const bool look = t.active[g] && t.rplayer[g] == 1 && a >= 0 && a < A;
-    const uint8_t* rb = t.rboard + (size_t)g * A;
-    for (int i = lane; i < A; i += 64) board[i] = rb[i];
-    __syncthreads();
-    int f = 0;
-    if (look && board[a] == 0) {
-        const bool base = __ballot(gomoku_base_shapes(board, t.bs, t.renju, t.omok, lane, 64)) != 0ULL;
-        f = gomoku_forbidden(board, t.bs, t.renju, t.omok, a, base);
-    }
-    if (lane == 0) bad[g] = f;
-}
-
 // K6: copy the subtree of the (new) root into the other arena, breadth first.
 // Subtree reuse: BFS copy of the new root's subtree into the other arena (children of a node stay
 // contiguous and in order; node k of the copy came from src_of[k]).  One 256-thread block per game
@@ -2035,44 +1896,66 @@ __global__ __launch_bounds__(64) void k_noise(TreeDev t, const float* noise, con
     }
 }
 
-// K8: fresh games (empty board, new tree; TT visits cleared by the caller).
-__global__ __launch_bounds__(64) void k_new_games(TreeDev t, const int* games, const int* seed_ids, int n,
-                                                  uint32_t eval_seed) {
-    const int idx = blockIdx.x;
-    const int lane = threadIdx.x;
-    if (idx >= n) return;
-    const int g = games[idx];
-    uint8_t* rb = t.rboard + (size_t)g * t.A;
-    for (int i = lane; i < t.A; i += 64) rb[i] = 0;
-    GamePtrs nd = game_nodes(t.nd, (size_t)g * t.ncap);
-    long long* cnt = t.cnt + (size_t)g * AZ_NCNT;
-    if (lane < CNT_EVALS_TOTAL) cnt[lane] = 0;
-    if (lane < 6) t.rhist[g * 6 + lane] = -1;
-    if (lane == 0) {
-        t.rplayer[g] = 1; t.rstones[g] = 0; t.rply[g] = 0; t.rfresh[g] = 1;
-        // Go: stones-only hash of the empty board; Gomoku under Renju / Omok: with the rules' feature keys
-        t.rhash[g] = t.game == GAME_GO ? 0ULL : (t.renju || t.omok) ? t.zplayer[0] ^ t.zconst : t.zplayer[0];
-        if (t.game == GAME_GO) { t.rko[g] = -1; t.rpass[g] = 0; t.rnposh[g] = 0; t.rcap[2 * g] = 0; t.rcap[2 * g + 1] = 0; }
-        t.rnode[g] = 0; t.atop[g] = 1; t.active[g] = 1; t.gresult[g] = R_ONGOING; t.ring_cur[g] = 0;
-        nd.N[0] = 0; nd.W[0] = 0.0f; nd.VL[0] = 0; nd.P[0] = 0.0f; nd.first[0] = -1; nd.act[0] = -1;
-        nd.cnt[0] = 0; nd.flag[0] = 0;
-        if (t.mt) {
-            // std::mt19937(seed + g) seeding (libstdc++ mersenne_twister_engine::seed)
-            uint32_t* st = t.mt + (size_t)g * 625;
-            st[0] = eval_seed + (uint32_t)(seed_ids ? seed_ids[idx] : g);
-            for (int i = 1; i < 624; ++i) st[i] = 1812433253u * (st[i - 1] ^ (st[i - 1] >> 30)) + (uint32_t)i;
-            st[624] = 624;
-        }
-    }
+// ---------------------------------------------------------------------------
+// Slot lifecycle: a slot's root position, the rules' verdict on a move, the move itself and the start of a
+// game, each written once.  k_new_games is "empty position, slot start", k_apply is "load, move, store, reuse
+// the child", k_open_games is "empty position, (judge, move) per ply, slot start" and k_illegal_moves is
+// "load, judge": whichever entry point reaches a position, the same code made it.
+namespace {
+// The root position of one slot -- what the r* arrays (tree.h) hold for it -- in wave-uniform registers.
+struct RootPos {
+    int player, stones, ply, res;    // side to move; stones placed; plies played (Go: passes too); GameResult
+    int h6[6];                       // last moves, [0] most recent, -1 none
+    uint64_t hash;                   // Gomoku: the position's Zobrist hash; Go: the stones-only hash
+    int ko, passes, cap[2], nh;      // Go: ko point, consecutive passes, captures by black / white, rposh entries
+};
+
+// The start position.  Go: the stones-only hash of the empty board; Gomoku: Black to move, under Renju / Omok
+// with the rules' feature keys.
+__device__ __forceinline__ RootPos root_empty(const TreeDev& t) {
+    RootPos s;
+    s.player = 1; s.stones = 0; s.ply = 0; s.res = R_ONGOING;
+    for (int i = 0; i < 6; ++i) s.h6[i] = -1;
+    s.hash = t.game == GAME_GO ? 0ULL : (t.renju || t.omok) ? t.zplayer[0] ^ t.zconst : t.zplayer[0];
+    s.ko = -1; s.passes = 0; s.cap[0] = 0; s.cap[1] = 0; s.nh = 0;
+    return s;
 }
 
-namespace {
+__device__ __forceinline__ RootPos root_load(const TreeDev& t, int g) {
+    RootPos s;
+    s.player = t.rplayer[g]; s.stones = t.rstones[g]; s.ply = t.rply[g]; s.res = t.gresult[g];
+    for (int i = 0; i < 6; ++i) s.h6[i] = t.rhist[g * 6 + i];
+    s.hash = t.rhash[g];
+    s.ko = -1; s.passes = 0; s.cap[0] = 0; s.cap[1] = 0; s.nh = 0;
+    if (t.game == GAME_GO) {
+        s.ko = t.rko[g]; s.passes = t.rpass[g]; s.cap[0] = t.rcap[2 * g]; s.cap[1] = t.rcap[2 * g + 1];
+        s.nh = t.rnposh[g];
+    }
+    return s;
+}
+
+// The position and its board (LDS, complete) into slot g: a finished game stops searching, and only a game
+// without a ply is fresh.  Every lane of the wave calls it.
+__device__ __forceinline__ void root_store(const TreeDev& t, int g, int lane, const RootPos& s, const uint8_t* board) {
+    uint8_t* rb = t.rboard + (size_t)g * t.A;
+    for (int i = lane; i < t.A; i += 64) rb[i] = board[i];
+    if (lane != 0) return;
+    t.rplayer[g] = s.player; t.rstones[g] = s.stones; t.rply[g] = s.ply; t.rfresh[g] = s.ply == 0;
+    for (int i = 0; i < 6; ++i) t.rhist[g * 6 + i] = s.h6[i];
+    t.rhash[g] = s.hash;
+    if (t.game == GAME_GO) {
+        t.rko[g] = s.ko; t.rpass[g] = s.passes; t.rcap[2 * g] = s.cap[0]; t.rcap[2 * g + 1] = s.cap[1];
+        t.rnposh[g] = s.nh;
+    }
+    t.gresult[g] = s.res; t.active[g] = s.res == R_ONGOING;
+}
+
 // One Go stone move against the rules, as getLegalMoves judges its candidates (go_legal above: the same
 // suicide test and the same resulting-position hash -- the mover to move, the old ko point -- against the
 // position history hist[0, nh)).  go_groups(.., &keys) must have run on the board; every lane of the wave
 // calls it with the same arguments and gets the same answer: an AZ_OPEN_* reason, 0 when the move is legal.
-__device__ int go_move_reason(const TreeDev& t, const uint8_t* b, const GoLds& L, int lane, int a, int player, int ko,
-                              uint64_t bh, const uint64_t* hist, int nh) {
+__device__ __forceinline__ int go_move_reason(const TreeDev& t, const uint8_t* b, const GoLds& L, int lane, int a, int player,
+                                              int ko, uint64_t bh, const uint64_t* hist, int nh) {
     const int A = t.A;
     if (b[a] != 0) return AZ_OPEN_OCCUPIED;
     if (a == ko) return AZ_OPEN_KO;
@@ -2098,12 +1981,150 @@ __device__ int go_move_reason(const TreeDev& t, const uint8_t* b, const GoLds& L
     for (int r = lane; r < nh; r += 64) hit |= hist[r] == hc;
     return __ballot(hit) != 0ULL ? AZ_OPEN_SUPERKO : 0;
 }
+
+// The judge: action a on position s (its board in LDS, complete; Go's position history in ph[0, s.nh))
+// against the rules, where make_move / makeMove of the reference throw (gomoku_state.cpp:697-703,
+// go_state.cpp:192-200) -- the AZ_OPEN_* reason, 0 when the move is legal (Go: the pass always is).  Every
+// lane of the wave calls it with the same arguments and gets the same answer.
+__device__ __forceinline__ int move_reason(const TreeDev& t, const RootPos& s, const uint8_t* board, GoLds& gl, int lane,
+                                           int a, const uint64_t* ph) {
+    const bool go = t.game == GAME_GO;
+    if (s.res != R_ONGOING) return AZ_OPEN_ENDED;
+    if (a < (go ? -1 : 0) || a >= t.A) return AZ_OPEN_RANGE;
+    if (go) {
+        if (a < 0) return 0;
+        GoKeys gk;
+        go_keys(t, board, s.player, lane, gk);
+        go_groups(t, board, gl, lane, 64, &gk);
+        return go_move_reason(t, board, gl, lane, a, s.player, s.ko, s.hash, ph, s.nh);
+    }
+    if (board[a] != 0) return AZ_OPEN_OCCUPIED;
+    if ((t.renju || t.omok) && s.player == 1) {
+        const bool base = __ballot(gomoku_base_shapes(board, t.bs, t.renju, t.omok, lane, 64)) != 0ULL;
+        if (gomoku_forbidden(board, t.bs, t.renju, t.omok, a, base)) return AZ_OPEN_FORBIDDEN;
+    }
+    return 0;
+}
+
+// lane 0's value on every lane, after a branch only lane 0 took
+__device__ __forceinline__ int lane0(int v) { return __builtin_amdgcn_readfirstlane(v); }
+
+// The move: legal action a turns s and its board (LDS) into the position after it, GomokuState::make_move
+// (gomoku_state.cpp:681-722) / GoState::makeMove (go_state.cpp:192-257) with the result of the new position.
+// Go: captures stay on lane 0 (go_play_seq); a stone move under superko pushes the new position onto the
+// history ph[0, s.nh) of capacity hcap (simple ko keeps none); two passes end the game (go_result_seq).
+// Gomoku: a five, the full board, or -- Renju / Omok -- Black left without a legal cell (is_stalemate,
+// gomoku_state.cpp:506-521; forb: LDS room for that mask, which nothing reads afterwards: the selection
+// builds the mask of the leaf it expands).  Every lane of the wave calls it with the same arguments; the
+// board is complete again on return.
+__device__ __forceinline__ void root_move(const TreeDev& t, RootPos& s, uint8_t* board, GoLds& gl, uint64_t* forb, int lane,
+                                          int a, uint64_t* ph, int hcap) {
+    const int A = t.A, p = s.player;
+    if (t.game == GAME_GO) {
+        go_clear_marks(gl, A, lane);
+        int k = s.ko, ps = s.passes, cap[2] = {s.cap[0], s.cap[1]}, nh = s.nh, res = R_ONGOING;
+        uint64_t bh = s.hash;
+        if (lane == 0) {
+            if (go_play_seq(t, board, gl, a, p, k, ps, bh, nullptr, cap) && t.superko) {
+                if (nh >= hcap) atomicOr(t.err, ERR_HIST);
+                else ph[nh++] = go_hash(t, bh, p, k);
+            }
+            if (ps >= 2) res = go_result_seq(t, board, gl, cap);
+        }
+        s.ko = lane0(k); s.passes = lane0(ps); s.cap[0] = lane0(cap[0]); s.cap[1] = lane0(cap[1]); s.nh = lane0(nh);
+        s.res = lane0(res); s.hash = lane_read64(bh, 0);
+        s.stones += a >= 0 ? 1 : 0;
+        __syncthreads();                          // lane 0's board for every lane
+    } else {
+        __syncthreads();                          // the judging reads of the board are over
+        if (lane == 0) board[a] = (uint8_t)p;
+        __syncthreads();
+        s.stones += 1;
+        if (five_at_wave(board, t.bs, a, p, lane)) s.res = p == 1 ? R_WIN1 : R_WIN2;
+        else if (s.stones >= A) s.res = R_DRAW;
+        else if ((t.renju || t.omok) && p == 2 && forbidden_mask_wave(t, board, lane, forb) == 0) s.res = R_DRAW;
+        s.hash ^= t.zpiece[(size_t)(p - 1) * A + a] ^ t.zplayer[p - 1] ^ t.zplayer[2 - p];
+    }
+    for (int j = 5; j > 0; --j) s.h6[j] = s.h6[j - 1];
+    s.h6[0] = a;
+    s.player = 3 - p;
+    s.ply += 1;
+}
+
+// A game starts in slot g at position s: a new tree (one root node), the game's counters at zero, the
+// RANDOM evaluator's generator seeded for the game's stream id (std::mt19937(eval_seed + id)), then the
+// position.  TT visits are cleared by the caller (k_tt_clear).  Every lane of the wave calls it.
+__device__ __forceinline__ void slot_start(const TreeDev& t, int g, int lane, const RootPos& s, const uint8_t* board,
+                                           uint32_t seed) {
+    long long* cnt = t.cnt + (size_t)g * AZ_NCNT;
+    if (lane < CNT_EVALS_TOTAL) cnt[lane] = 0;
+    if (lane == 0) {
+        t.rnode[g] = 0; t.atop[g] = 1; t.ring_cur[g] = 0;
+        node_clear(game_nodes(t.nd, (size_t)g * t.ncap), 0);
+        if (t.mt) mt_seed(t.mt + (size_t)g * 625, seed);
+    }
+    root_store(t, g, lane, s, board);
+}
+
+// updateWithMove's subtree reuse (parallel_mcts.cpp:1065-1108): the child that played `a`
+// becomes the root, else a fresh root node.  Lane 0.
+// returns the flag of the new root (0 for a fresh node)
+__device__ uint8_t reuse_child(const TreeDev& t, int g, const GamePtrs& nd, int a) {
+    const int root = t.rnode[g];
+    const int fc = nd.first[root], nc = nd.cnt[root];
+    int child = -1;
+    for (int i = 0; i < nc; ++i) if (nd.act[fc + i] == a) { child = fc + i; break; }
+    if (child < 0) {
+        child = t.atop[g];
+        if (child + 1 > t.ncap) { atomicOr(t.err, ERR_NODES); child = 0; }
+        else t.atop[g] = child + 1;
+        node_clear(nd, child);
+        t.rnode[g] = child;
+        return 0;
+    }
+    t.rnode[g] = child;
+    return nd.flag[child];
+}
 }  // namespace
 
-// Go: the moves az_search_apply is about to commit, against the rules (occupied point, suicide, the ko
-// point, a superko repeat) -- bad[g] = the AZ_OPEN_* reason, 0 for a legal move, a pass, a skipped or a
-// finished game.  One wave per game.
-__global__ __launch_bounds__(64) void k_go_illegal_moves(TreeDev t, const int* actions, int* bad) {
+// K5: makeMove + updateWithMove; terminal test of the new root (game loop condition).
+// rexp[g] (optional): 1 when the game's root after the move needs no root expansion (expanded or
+// terminal, or the game is not playing) -- the host then skips the no-op root steps
+__global__ __launch_bounds__(64) void k_apply(TreeDev t, const int* actions, int* terminal, int* result, int* rexp) {
+    const int g = blockIdx.x;
+    const int lane = threadIdx.x;
+    __shared__ uint8_t board[AZ_MAXA];
+    __shared__ GoLds gl;
+    __shared__ uint64_t forb[AZ_FORB_WORDS];
+    if (g >= t.G) return;
+    const int a = actions[g];
+    const int A = t.A;
+    GamePtrs nd = game_nodes(t.nd, (size_t)g * t.ncap);
+    if (!t.active[g] || a < (t.game == GAME_GO ? -1 : 0) || a >= A) {          // Go: -1 is the pass
+        if (lane == 0) {
+            terminal[g] = t.active[g] ? 0 : 1; result[g] = t.gresult[g];
+            if (rexp) rexp[g] = t.active[g] ? ((nd.flag[t.rnode[g]] & (FL_EXPANDED | FL_TERMINAL)) != 0) : 1;
+        }
+        return;
+    }
+    RootPos s = root_load(t, g);
+    const uint8_t* rb = t.rboard + (size_t)g * A;
+    for (int i = lane; i < A; i += 64) board[i] = rb[i];
+    __syncthreads();
+    root_move(t, s, board, gl, forb, lane, a, t.rposh + (size_t)g * t.hmax, t.hmax);
+    root_store(t, g, lane, s, board);
+    if (lane == 0) {
+        terminal[g] = s.res != R_ONGOING;
+        result[g] = s.res;
+        const uint8_t fl = reuse_child(t, g, nd, a);
+        if (rexp) rexp[g] = s.res != R_ONGOING || (fl & (FL_EXPANDED | FL_TERMINAL)) != 0;
+    }
+}
+
+// The moves az_search_apply is about to commit, against the rules: bad[g] = the judge's AZ_OPEN_* reason
+// for actions[g] on game g's root position, 0 for a legal move, a pass, no move or a game that is not
+// playing.  One wave per game; launched on a Go handle and on a Gomoku handle with rules.
+__global__ __launch_bounds__(64) void k_illegal_moves(TreeDev t, const int* actions, int* bad) {
     const int g = blockIdx.x;
     const int lane = threadIdx.x;
     __shared__ uint8_t board[AZ_MAXA];
@@ -2111,23 +2132,32 @@ __global__ __launch_bounds__(64) void k_go_illegal_moves(TreeDev t, const int* a
     if (g >= t.G) return;
     const int a = actions[g], A = t.A;
     if (!t.active[g] || a < 0 || a >= A) { if (lane == 0) bad[g] = 0; return; }
+    const RootPos s = root_load(t, g);
     const uint8_t* rb = t.rboard + (size_t)g * A;
     for (int i = lane; i < A; i += 64) board[i] = rb[i];
     __syncthreads();
-    const int p = t.rplayer[g];
-    GoKeys gk;
-    go_keys(t, board, p, lane, gk);
-    go_groups(t, board, gl, lane, 64, &gk);
-    const int why = go_move_reason(t, board, gl, lane, a, p, t.rko[g], t.rhash[g], t.rposh + (size_t)g * t.hmax,
-                                   t.superko ? t.rnposh[g] : 0);
+    const int why = move_reason(t, s, board, gl, lane, a, t.rposh + (size_t)g * t.hmax);
     if (lane == 0) bad[g] = why;
 }
 
+// K8: fresh games (empty board, new tree; TT visits cleared by the caller).
+__global__ __launch_bounds__(64) void k_new_games(TreeDev t, const int* games, const int* seed_ids, int n,
+                                                  uint32_t eval_seed) {
+    const int idx = blockIdx.x;
+    const int lane = threadIdx.x;
+    __shared__ uint8_t board[AZ_MAXA];
+    if (idx >= n) return;
+    const int g = games[idx];
+    for (int i = lane; i < t.A; i += 64) board[i] = 0;
+    __syncthreads();
+    slot_start(t, g, lane, root_empty(t), board, eval_seed + (uint32_t)(seed_ids ? seed_ids[idx] : g));
+}
+
 // Openings: fresh games in the listed slots, each advanced by its own move sequence in one launch -- what
-// k_new_games and one k_apply (+ k_compact) per move leave behind, field for field, with every move judged
-// against the rules first.  One wave per listed slot; the board lives in LDS as in k_apply, Go's captures
-// stay on lane 0 (go_play_seq).  o.rep[AZ_OPEN_REP idx ..]: {first bad ply or -1, its AZ_OPEN_* reason, the
-// game still playing after the opening, its GameResult, the random plies played}.  dry: the same pass without a
+// k_new_games and one k_apply (+ k_compact) per move leave behind, field for field (the same routines make
+// it), with every move judged against the rules first.  One wave per listed slot; the board lives in LDS.
+// o.rep[AZ_OPEN_REP idx ..]: {first bad ply or -1, its AZ_OPEN_* reason, the game still playing after the
+// opening, its GameResult, the random plies played}.  dry: the same pass without a
 // single store to the slot (Go's position history then grows in o.hist, o.hstride per entry, instead of the
 // slot's own); the host validates with it, so the storing pass never meets a bad move.
 // Random plies: after the sequence up to o.rplies further plies are drawn here.  Ply j (the game's real ply
@@ -2143,50 +2173,40 @@ __global__ __launch_bounds__(64) void k_open_games(TreeDev t, OpenDev o) {
     __shared__ GoLds gl;
     __shared__ uint64_t forb[AZ_FORB_WORDS];
     __shared__ int legal[AZ_MAXNA];
-    __shared__ struct { uint64_t bh; int ko, passes, cap[2], nh, res; } S;
     const int n = o.n, dry = o.dry;
     if (idx >= n) return;
     const int g = o.games ? o.games[idx] : 0;
     const int A = t.A;
     const bool go = t.game == GAME_GO;
-    const bool rules = !go && (t.renju || t.omok);
     const int seq = o.seq_of ? o.seq_of[idx] : idx;
     const int nm = o.n_moves ? o.n_moves[seq] : 0;
     const int* mv = o.moves + (size_t)seq * o.stride;
     const int sid = o.seed_ids ? o.seed_ids[idx] : g;
     const uint32_t rid = (uint32_t)(o.rand_ids ? o.rand_ids[idx] : sid);
-    int* rep = o.rep + AZ_OPEN_REP * idx;
     uint64_t* ph = dry ? o.hist + (size_t)idx * o.hstride : t.rposh + (size_t)g * t.hmax;
+    const int hcap = dry ? o.hstride : t.hmax;
     for (int i = lane; i < A; i += 64) board[i] = 0;
-    // the game's state, the same on every lane (Go: lane 0 plays, the others read S after the barrier)
-    int p = 1, stones = 0, res = R_ONGOING, ko = -1, passes = 0, nh = 0, cap0 = 0, cap1 = 0;
-    int h6[6] = {-1, -1, -1, -1, -1, -1};
-    uint64_t hash = go ? 0ULL : rules ? t.zplayer[0] ^ t.zconst : t.zplayer[0];
+    RootPos s = root_empty(t);                    // the game's position, the same on every lane
     int bad = -1, why = 0, nrand = 0;
-    if (lane == 0) gl.nph = 0;                    // go_legal_hist: no path pushes, the history is ph[0, nh)
+    if (lane == 0) gl.nph = 0;                    // go_legal_hist: no path pushes, the history is ph[0, s.nh)
     __syncthreads();
     for (int i = 0; i < nm + o.rplies; ++i) {
         int a;
         if (i >= nm) {
             // a random ply: the side to move's legal moves in ascending order, one picked by the game's stream
-            if (res != R_ONGOING) break;
-            uint32_t c[4] = {rid, (uint32_t)i, 0u, 0u}, k0 = o.key_lo, k1 = o.key_hi;
-            for (int round = 0; round < 10; ++round) {          // Philox4x32-10, as the replay plan's (replay.hip)
-                const uint64_t p0 = (uint64_t)0xD2511F53u * c[0], p1 = (uint64_t)0xCD9E8D57u * c[2];
-                const uint32_t n0 = (uint32_t)(p1 >> 32) ^ c[1] ^ k0, n2 = (uint32_t)(p0 >> 32) ^ c[3] ^ k1;
-                c[0] = n0; c[1] = (uint32_t)p1; c[2] = n2; c[3] = (uint32_t)p0;
-                k0 += 0x9E3779B9u; k1 += 0xBB67AE85u;
-            }
+            if (s.res != R_ONGOING) break;
+            uint32_t c[4] = {rid, (uint32_t)i, 0u, 0u};
+            philox4x32_10(c, o.key_lo, o.key_hi);
             int nl;
             if (go) {
                 GoKeys gk;
-                go_keys(t, board, p, lane, gk);
+                go_keys(t, board, s.player, lane, gk);
                 go_groups(t, board, gl, lane, 64, &gk);
-                nl = go_legal_hist(t, ph, t.superko ? nh : 0, lane, board, gl, p, ko, hash, legal, gk) - 1;   // [0]: the pass
+                nl = go_legal_hist(t, ph, t.superko ? s.nh : 0, lane, board, gl, s.player, s.ko, s.hash, legal, gk) - 1;   // [0]: the pass
                 if (nl <= 0) break;
                 a = legal[1 + (int)(((uint64_t)c[0] * (uint64_t)nl) >> 32)];
             } else {
-                const bool masked = rules && p == 1;
+                const bool masked = (t.renju || t.omok) && s.player == 1;
                 if (masked) forbidden_mask_wave(t, board, lane, forb);
                 __syncthreads();
                 nl = 0;
@@ -2203,91 +2223,32 @@ __global__ __launch_bounds__(64) void k_open_games(TreeDev t, OpenDev o) {
             }
         } else {
             a = mv[i];
+            why = move_reason(t, s, board, gl, lane, a, ph);   // a random ply is legal by construction
+            if (why) { bad = i; break; }
         }
-        if (i >= nm) why = 0;
-        else if (res != R_ONGOING) why = AZ_OPEN_ENDED;
-        else if (a < (go ? -1 : 0) || a >= A) why = AZ_OPEN_RANGE;
-        else if (go) {
-            if (a >= 0) {
-                GoKeys gk;
-                go_keys(t, board, p, lane, gk);
-                go_groups(t, board, gl, lane, 64, &gk);
-                why = go_move_reason(t, board, gl, lane, a, p, ko, hash, ph, nh);
-            }
-        } else if (board[a] != 0) why = AZ_OPEN_OCCUPIED;
-        else if (rules && p == 1) {
-            const bool base = __ballot(gomoku_base_shapes(board, t.bs, t.renju, t.omok, lane, 64)) != 0ULL;
-            if (gomoku_forbidden(board, t.bs, t.renju, t.omok, a, base)) why = AZ_OPEN_FORBIDDEN;
-        }
-        if (why) { bad = i; break; }
-        if (go) {
-            // GoState::makeMove, as k_apply
-            go_clear_marks(gl, A, lane);
-            if (lane == 0) {
-                int k = ko, ps = passes, cap[2] = {cap0, cap1}, m = nh;
-                uint64_t bh = hash;
-                if (go_play_seq(t, board, gl, a, p, k, ps, bh, nullptr, cap) && t.superko) ph[m++] = go_hash(t, bh, p, k);
-                S.bh = bh; S.ko = k; S.passes = ps; S.cap[0] = cap[0]; S.cap[1] = cap[1]; S.nh = m;
-                S.res = ps >= 2 ? go_result_seq(t, board, gl, cap) : R_ONGOING;
-            }
-            __syncthreads();
-            hash = S.bh; ko = S.ko; passes = S.passes; cap0 = S.cap[0]; cap1 = S.cap[1]; nh = S.nh; res = S.res;
-            stones += a >= 0 ? 1 : 0;
-            __syncthreads();                      // S is read before the next ply rewrites it
-        } else {
-            // GomokuState::make_move, as k_apply
-            __syncthreads();                      // the judging reads of the board are over
-            if (lane == 0) board[a] = (uint8_t)p;
-            __syncthreads();
-            int r = R_ONGOING;
-            if (five_at_wave(board, t.bs, a, p, lane)) r = p == 1 ? R_WIN1 : R_WIN2;
-            else if (stones + 1 >= A) r = R_DRAW;
-            else if (rules && p == 2 && forbidden_mask_wave(t, board, lane, forb) == 0) r = R_DRAW;   // is_stalemate
-            if (i >= nm && r != R_ONGOING) {      // a random ply never ends the game: the stone comes off again
+        const RootPos before = s;
+        root_move(t, s, board, gl, forb, lane, a, ph, hcap);
+        if (i >= nm) {
+            if (s.res != R_ONGOING) {
+                // a random ply never ends the game: the stone comes off again (Gomoku; Go's picks leave out
+                // the pass, the one move that ends a game)
                 __syncthreads();
                 if (lane == 0) board[a] = 0;
                 __syncthreads();
+                s = before;
                 break;
             }
-            hash ^= t.zpiece[(size_t)(p - 1) * A + a] ^ t.zplayer[p - 1] ^ t.zplayer[2 - p];
-            stones += 1;
-            res = r;
-        }
-        for (int j = 5; j > 0; --j) h6[j] = h6[j - 1];
-        h6[0] = a;
-        p = 3 - p;
-        if (i >= nm) {
             if (lane == 0 && o.picks) o.picks[(size_t)idx * o.rplies + nrand] = a;
             ++nrand;
         }
     }
-    const int np = nm + nrand;                    // plies played
     if (lane == 0) {
-        rep[0] = bad; rep[1] = why; rep[2] = bad < 0 && res == R_ONGOING; rep[3] = res; rep[4] = nrand;
+        int* rep = o.rep + AZ_OPEN_REP * idx;
+        rep[0] = bad; rep[1] = why; rep[2] = bad < 0 && s.res == R_ONGOING; rep[3] = s.res; rep[4] = nrand;
     }
     if (dry || bad >= 0) return;
     __syncthreads();
-    uint8_t* rb = t.rboard + (size_t)g * A;
-    for (int i = lane; i < A; i += 64) rb[i] = board[i];
-    GamePtrs nd = game_nodes(t.nd, (size_t)g * t.ncap);
-    long long* cnt = t.cnt + (size_t)g * AZ_NCNT;
-    if (lane < CNT_EVALS_TOTAL) cnt[lane] = 0;
-    if (lane == 0) {
-        for (int j = 0; j < 6; ++j) t.rhist[g * 6 + j] = h6[j];
-        t.rplayer[g] = p; t.rstones[g] = stones; t.rply[g] = np; t.rfresh[g] = np == 0;
-        t.rhash[g] = hash;
-        if (go) { t.rko[g] = ko; t.rpass[g] = passes; t.rnposh[g] = nh; t.rcap[2 * g] = cap0; t.rcap[2 * g + 1] = cap1; }
-        t.rnode[g] = 0; t.atop[g] = 1; t.active[g] = res == R_ONGOING; t.gresult[g] = res; t.ring_cur[g] = 0;
-        nd.N[0] = 0; nd.W[0] = 0.0f; nd.VL[0] = 0; nd.P[0] = 0.0f; nd.first[0] = -1; nd.act[0] = -1;
-        nd.cnt[0] = 0; nd.flag[0] = 0;
-        if (t.mt) {
-            // std::mt19937(seed + id) seeding, as k_new_games
-            uint32_t* st = t.mt + (size_t)g * 625;
-            st[0] = o.eval_seed + (uint32_t)sid;
-            for (int i = 1; i < 624; ++i) st[i] = 1812433253u * (st[i - 1] ^ (st[i - 1] >> 30)) + (uint32_t)i;
-            st[624] = 624;
-        }
-    }
+    slot_start(t, g, lane, s, board, o.eval_seed + (uint32_t)sid);
 }
 
 // Every slot of a new handle as an idle game: a valid root (node 0 of both arenas, no children),
@@ -2298,12 +2259,8 @@ __global__ void k_init_slots(TreeDev t, Nodes other) {
     if (g >= t.G) return;
     t.rnode[g] = 0; t.atop[g] = 1; t.active[g] = 0; t.gresult[g] = R_ONGOING; t.ring_cur[g] = 0;
     t.rplayer[g] = 1; t.rstones[g] = 0; t.rply[g] = 0; t.rfresh[g] = 1; t.rhash[g] = 0;
-    const Nodes* ar[2] = {&t.nd, &other};
-    for (int k = 0; k < 2; ++k) {
-        GamePtrs nd = game_nodes(*ar[k], (size_t)g * t.ncap);
-        nd.N[0] = 0; nd.W[0] = 0.0f; nd.VL[0] = 0; nd.P[0] = 0.0f; nd.first[0] = -1; nd.act[0] = -1;
-        nd.cnt[0] = 0; nd.flag[0] = 0;
-    }
+    node_clear(game_nodes(t.nd, (size_t)g * t.ncap), 0);
+    node_clear(game_nodes(other, (size_t)g * t.ncap), 0);
 }
 
 // TT clear for the listed games (visits == 0 marks an empty slot).

@@ -252,7 +252,7 @@ typedef struct az_search_opts {
  * (az_search_new_games*, az_search_set_params, az_search_set_options, az_search_set_net and az_search_clear_tt
  * leave them alone).  The rules are the reference's with its rule checker's accessor recursion repaired
  * (DESIGN.md section 6): the cells forbidden to Black are missing from its legal moves, Black to move with
- * no legal cell is a DRAW, az_search_apply refuses a forbidden cell (AZ_ERR_ARG), and the "renju" / "omok"
+ * no legal cell is a DRAW, az_search_apply refuses a forbidden or an occupied cell (AZ_ERR_ARG), and the "renju" / "omok"
  * feature keys are part of every position's hash.  Renju decides when both are set.  pro_long_opening != 0
  * is refused (AZ_ERR_ARG): its legal order follows the reference's hash-set rehash history. */
 typedef struct az_gomoku_rules {

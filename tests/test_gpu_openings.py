@@ -156,6 +156,45 @@ def test_gpu_openings_renju(engine):
         m.close()
 
 
+# One judge behind both entry points: (rules, the plies before, the refused move, the word of its reason)
+VERDICTS = {
+    # White at 0 between Black 1 and 9, each with two liberties left: nothing is captured
+    "go-suicide": ("go", [1, 40, 9], 0, "suicide"),
+    "go-occupied": ("go", [1, 40, 9], 40, "occupied"),
+    "go-superko": ("go", KO_LIST, 1, "superko"),
+    "renju-forbidden": ("renju", RENJU_SEQ, 40, "forbidden"),
+    # Black's own stone: GomokuState::make_move throws "already occupied" whatever the rules
+    "renju-occupied": ("renju", RENJU_SEQ, 37, "occupied"),
+}
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("case", list(VERDICTS))
+def test_gpu_openings_both_entry_points_give_the_same_verdict(engine, case):
+    """The same position reached by an opening and move by move: the move the rules refuse is refused as the next
+    ply of the sequence and by az_search_apply, for the same reason, and both handles stay as they were."""
+    import az_amd
+    from az_amd import _lib
+    rules, prefix, bad, why = VERDICTS[case]
+    kw = dict(game=az_amd.AZ_GAME_GO, go_superko=True) if rules == "go" else dict(gomoku_renju=True)
+    a, b = handle(engine, 1, **kw), handle(engine, 1, **kw)
+    try:
+        a.new_games_moves([prefix])
+        compose(b, [prefix], None)
+        before_a, before_b = snapshot(a), snapshot(b)
+        with pytest.raises(az_amd.AzError, match=rf"entry 0 .*ply {len(prefix)},.*{why}") as e:
+            a.new_games_moves([prefix + [bad]])
+        assert e.value.code == _lib.AZ_ERR_ARG
+        with pytest.raises(az_amd.AzError, match=why) as e:
+            b.updateWithMove(np.array([bad], np.int32))
+        assert e.value.code == _lib.AZ_ERR_ARG
+        assert snapshot(a) == before_a and snapshot(b) == before_b
+        play_both(a, b, rounds=1)                              # equal and playable after the refusals
+    finally:
+        a.close()
+        b.close()
+
+
 def raw_call(m, games, seqs, stride, n_moves=None):
     from az_amd import _lib
     games = np.asarray(games, np.int32)
