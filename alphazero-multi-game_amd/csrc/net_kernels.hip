@@ -421,26 +421,39 @@ void az_launch_rec_planes(const uint8_t* rec, float* dst, const int* eval_games,
     hipLaunchKernelGGL(k_rec_planes, dim3(2, maxB), dim3(256), 0, st, rec, dst, eval_games, n_eval, go, bs);
 }
 
-// softmax over A per row (predictBatch semantics; host-facing az_net_predict_batch)
+// softmax over A per row (predictBatch semantics; host-facing az_net_predict_batch): max-subtracted,
+// the sum sequential in fp32 from action 0 upwards (the reference's loop; the search's own softmax
+// adds in the same order, and its logged policies are compared with this one bit for bit).  Any A:
+// exp(logit - max) is staged in LDS a chunk of CH actions at a time, thread 0 carries the running
+// sum across the chunks in action order, and rows longer than one chunk recompute expf in the
+// output pass (the same value: same argument, same function).
 __global__ void k_softmax_rows(const float* logits, float* out, int A) {
-    const int b = blockIdx.x;
-    __shared__ float e[1024];
+    constexpr int CH = 1024;
+    const float* row = logits + (size_t)blockIdx.x * A;
+    float* dst = out + (size_t)blockIdx.x * A;
+    __shared__ float e[CH];
     __shared__ float s_sum, s_max;
     if (threadIdx.x == 0) {
         float mx = -3.402823466e38f;
-        for (int a = 0; a < A; ++a) mx = fmaxf(mx, logits[(size_t)b * A + a]);
+        for (int a = 0; a < A; ++a) mx = fmaxf(mx, row[a]);
         s_max = mx;
     }
     __syncthreads();
-    for (int a = threadIdx.x; a < A; a += blockDim.x) e[a] = expf(logits[(size_t)b * A + a] - s_max);
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        float s = 0.0f;
-        for (int a = 0; a < A; ++a) s += e[a];
-        s_sum = s;
+    float s = 0.0f;                                    // thread 0: the running sum
+    for (int c0 = 0; c0 < A; c0 += CH) {
+        const int n = min(CH, A - c0);
+        for (int i = threadIdx.x; i < n; i += blockDim.x) e[i] = expf(row[c0 + i] - s_max);
+        __syncthreads();
+        if (threadIdx.x == 0)
+            for (int i = 0; i < n; ++i) s += e[i];
+        __syncthreads();                               // e is rewritten by the next chunk
     }
+    if (threadIdx.x == 0) s_sum = s;
     __syncthreads();
-    for (int a = threadIdx.x; a < A; a += blockDim.x) out[(size_t)b * A + a] = s_sum > 0.0f ? e[a] / s_sum : e[a];
+    for (int a = threadIdx.x; a < A; a += blockDim.x) {
+        const float v = A <= CH ? e[a] : expf(row[a] - s_max);
+        dst[a] = s_sum > 0.0f ? v / s_sum : v;
+    }
 }
 
 // split-K reduction: C = act(sum_s part[s] + bias), slices summed in order (deterministic)
